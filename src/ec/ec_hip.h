@@ -230,6 +230,16 @@ struct GatedArgs {
 ucc_status_t staged_stage(const GatedArgs &a, hipStream_t s);
 ucc_status_t staged_reduce(const GatedArgs &a, hipStream_t s);
 ucc_status_t staged_gather(const GatedArgs &a, hipStream_t s);
+/* Fused zero-copy allreduce / reduce_scatter: ONE launch of a.nblocks
+ * blocks in place of staged_stage (1 block) + staged_reduce +
+ * staged_gather (1 block) resp. gated_wait_only. Host-target mode only
+ * (derive == 0). Takes the reduce launch's GatedArgs (peer_in = peers'
+ * user src, zc_write = 1 with peer_out = every rank's dst slice for
+ * allreduce; zc_write = 0 with my_out = my user dst for reduce_scatter)
+ * plus done_host/done_seq. Counter effects: phase 0 +1, phase 1
+ * +nblocks, and for allreduce phase 2 +1 — those of the launches it
+ * replaces. */
+ucc_status_t zc_allreduce(const GatedArgs &a, hipStream_t s);
 /* copy-engine gating (SDMA data path): pure wait on gw_phase/t_gather_wait
  * (1 block), and signal-phase-2-then-wait-team (full gated grid). */
 ucc_status_t gated_wait_only(const GatedArgs &a, hipStream_t s);

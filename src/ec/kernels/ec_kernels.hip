@@ -1238,6 +1238,314 @@ __global__ void k_gated_done(const GatedArgs a)
     }
 }
 
+/* ------------------------------- fused zero-copy allreduce (one launch) */
+/* gated_signal that tells the WHOLE block whether it was the last
+ * arriver of this launch (LDS broadcast), so the block can go on into a
+ * gated_wait together. Publishes no done_host. */
+__device__ __forceinline__ bool
+gated_signal_last(const GatedArgs &a, int phase, uint64_t sig_target)
+{
+    __shared__ int s_last;
+    /* every wave's stores have reached L2, then ONE release for the
+     * block (the acq_rel add below: a single L2 write-back per block
+     * instead of one per wave plus one — the write-backs of a grid's
+     * blocks queue up on their XCD's L2) */
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t v = __hip_atomic_fetch_add(
+                         a.local_flags +
+                             gated_idx(phase, a.slot, a.parity),
+                         1, __ATOMIC_ACQ_REL,
+                         __HIP_MEMORY_SCOPE_SYSTEM) +
+                     1;
+        const int last = v == sig_target;
+        if (last) {
+            /* same dropped-vmcnt guard as gated_signal */
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            for (int j = 0; j < a.nranks; j++) {
+                __hip_atomic_store(
+                    a.peer_flags[j] +
+                        gated_mirror_idx(phase, a.slot, a.parity,
+                                         a.rank),
+                    v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+        s_last = last;
+    }
+    __syncthreads();
+    return s_last != 0;
+}
+
+/* gated_wait on two phases at once with ONE acquire per block: wave 0
+ * polls both mirrors (local memory), invalidates, and the barrier
+ * orders every other wave's loads behind that invalidate. */
+__device__ __forceinline__ bool zc_wait2(const GatedArgs &a, int ph0,
+                                         uint64_t t0, int ph1,
+                                         uint64_t t1)
+{
+    __shared__ int s_err2;
+    if (threadIdx.x == 0) {
+        s_err2 = 0;
+    }
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        const int j = (int)threadIdx.x;
+        if (j < a.nranks) {
+            const uint64_t cap   = spin_cap(a.spin_limit);
+            uint64_t       spins = 0;
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const int      ph = k ? ph1 : ph0;
+                const uint64_t t  = k ? t1 : t0;
+                if (t == 0) {
+                    continue;
+                }
+                const uint64_t *f =
+                    a.pull_wait
+                        ? a.peer_flags[j] + gated_idx(ph, a.slot, a.parity)
+                        : a.local_flags +
+                              gated_mirror_idx(ph, a.slot, a.parity, j);
+                while (sys_load(f) < t) {
+                    if (++spins > cap) {
+                        sys_store(a.error_word, 1);
+                        s_err2 = 1;
+                        break;
+                    }
+                    __builtin_amdgcn_s_sleep(2);
+                }
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+    return s_err2 == 0;
+}
+
+/* peer unroll bound of the fused kernel by batching depth: the launcher
+ * only picks U with U * nranks <= kMaxRanks, so the uniform `s < n`
+ * guard never has to cover more peers than this and the two pack
+ * buffers of the pipelined loop stay at U * NR * 16 B per lane each. */
+template <int U> struct ZcPeers {
+    static constexpr int value = kMaxRanks / U > 0 ? kMaxRanks / U : 1;
+};
+
+/* issue one batch's U x n peer loads (no consumer in between) */
+template <typename P, int U, int NR>
+__device__ __forceinline__ void
+zc_batch_load(P (&x)[U][NR], const GatedArgs &a, int n, uint64_t i,
+              uint64_t str)
+{
+#pragma unroll
+    for (int s = 0; s < NR; s++) {
+        if (s < n) {
+            const P *src =
+                (const P *)((const uint8_t *)a.peer_in[s] + a.sl_b);
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                x[u][s] = src[i + (uint64_t)u * str];
+            }
+        }
+    }
+}
+
+/* convert, reduce ranks 0..n-1 in order, scale, store one loaded batch:
+ * the arithmetic of k_staged_reduce's batched loop, element for element */
+template <typename T, int OP, int VEC, int U, int NR, typename P>
+__device__ __forceinline__ void
+zc_batch_reduce_store(const P (&x)[U][NR], const GatedArgs &a, int n,
+                      uint64_t i, uint64_t str)
+{
+    using A = typename Cvt<T>::A;
+    A r[U][VEC];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        vload<T, OP, VEC, A>(x[u][0], r[u]);
+    }
+#pragma unroll
+    for (int s = 1; s < NR; s++) {
+        if (s < n) {
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                vaccum<T, OP, VEC, A>(r[u], x[u][s]);
+            }
+        }
+    }
+    P o[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        vstore<T, OP, VEC, A>(o[u], r[u], a.alpha);
+    }
+    if (a.zc_write) {
+#pragma unroll
+        for (int s = 0; s < NR; s++) {
+            if (s < n) {
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    ((P *)a.peer_out[s])[i + (uint64_t)u * str] = o[u];
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            ((P *)a.my_out)[i + (uint64_t)u * str] = o[u];
+        }
+    }
+}
+
+/* One launch per zero-copy post (host-target mode only): the stage
+ * signal, the reduce and the completion wait of the three-kernel pattern
+ * in one grid of a.nblocks blocks. Counter effects are those of the
+ * three launches (phase 0 +1, phase 1 +B, phase 2 +1), so every other
+ * gated collective composes with it on the shared (slot,parity)
+ * counters. zc_write = 1: allreduce, my reduced slice goes into every
+ * rank's dst. zc_write = 0: reduce_scatter, my slice goes to my_out only
+ * and phase 2 is neither waited on nor signalled. See
+ * docs/GATED_PIPELINE.md "Fused zero-copy allreduce". */
+template <typename T, int OP, int VEC, int U>
+__global__ void __launch_bounds__(256) k_zc_allreduce(const GatedArgs a)
+{
+    using A          = typename Cvt<T>::A;
+    using P          = Pack<T, OP, VEC>;
+    constexpr int NR = ZcPeers<U>::value;
+    /* entry: block 0 is this rank's stage launch — area-reuse waits
+     * (already satisfied in steady state), then "my stream reached this
+     * post" on phase 0 (+1, so this one increment is the last arriver
+     * and pushes the mirrors) */
+    if (blockIdx.x == 0) {
+        if (!zc_wait2(a, 1, a.t_sw_reduce, 2, a.t_sw_gather)) {
+            return;
+        }
+        gated_signal(a, 0, a.t_sig_stage, /*pub_done=*/false);
+    }
+    if (!zc_wait2(a, 0, a.t_stage, 2, a.t_prev_gather)) {
+        return;
+    }
+    const uint64_t cnt = (a.sl_e - a.sl_b) / sizeof(T);
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t str = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t nv  = cnt / VEC;
+    /* 2 <= nranks <= NR (launcher-checked). At NR == 2 that pins n, so
+     * the uniform peer guards fold away. This is what lets the pipeline
+     * work: behind a branch that may or may not have issued loads the
+     * compiler can only wait for vmcnt(0), which would drain the batch
+     * just issued along with the one about to be consumed. */
+    const int n = NR == 2 ? 2 : a.nranks;
+    __builtin_assume(n >= 2 && n <= NR);
+    uint64_t i = tid;
+    if (U > 1) {
+        /* software-pipelined batches over two pack buffers: the loads
+         * of batch k+1 are in flight while batch k is converted, added
+         * and stored, so the bytes-in-flight figure of k_staged_reduce
+         * holds through the whole iteration instead of only between
+         * its load and its first use (one wave per SIMD here: no
+         * sibling wave covers that bubble). Batches touch disjoint
+         * elements, so in-place (dst == src) stays correct. */
+        const uint64_t bs   = (uint64_t)U * str;
+        const uint64_t tail = (uint64_t)(U - 1) * str;
+        if (i + tail < nv) {
+            P xa[U][NR], xb[U][NR];
+            /* prologue: xa <- batch i. The steady-state body below has
+             * no branch around a load (see the note on n above): it
+             * runs while batches i, i+bs and i+2bs all exist, and on
+             * exit xa again holds batch i. */
+            zc_batch_load<P, U, NR>(xa, a, n, i, str);
+            while (i + 2 * bs + tail < nv) {
+                zc_batch_load<P, U, NR>(xb, a, n, i + bs, str);
+                zc_batch_reduce_store<T, OP, VEC, U, NR, P>(xa, a, n, i,
+                                                            str);
+                zc_batch_load<P, U, NR>(xa, a, n, i + 2 * bs, str);
+                zc_batch_reduce_store<T, OP, VEC, U, NR, P>(xb, a, n,
+                                                            i + bs, str);
+                i += 2 * bs;
+            }
+            /* epilogue: one or two full batches left */
+            if (i + bs + tail < nv) {
+                zc_batch_load<P, U, NR>(xb, a, n, i + bs, str);
+                zc_batch_reduce_store<T, OP, VEC, U, NR, P>(xa, a, n, i,
+                                                            str);
+                zc_batch_reduce_store<T, OP, VEC, U, NR, P>(xb, a, n,
+                                                            i + bs, str);
+                i += 2 * bs;
+            } else {
+                zc_batch_reduce_store<T, OP, VEC, U, NR, P>(xa, a, n, i,
+                                                            str);
+                i += bs;
+            }
+        }
+    }
+    for (; i < nv; i += str) {
+        A r[VEC];
+        {
+            P acc = ((const P *)((const uint8_t *)a.peer_in[0] +
+                                 a.sl_b))[i];
+            vload<T, OP, VEC, A>(acc, r);
+        }
+#pragma unroll
+        for (int s = 1; s < NR; s++) {
+            if (s < n) {
+                P x = ((const P *)((const uint8_t *)a.peer_in[s] +
+                                   a.sl_b))[i];
+                vaccum<T, OP, VEC, A>(r, x);
+            }
+        }
+        P o;
+        vstore<T, OP, VEC, A>(o, r, a.alpha);
+        if (a.zc_write) {
+#pragma unroll
+            for (int s = 0; s < NR; s++) {
+                if (s < n) {
+                    ((P *)a.peer_out[s])[i] = o;
+                }
+            }
+        } else {
+            ((P *)a.my_out)[i] = o;
+        }
+    }
+    for (uint64_t t = nv * VEC + tid; t < cnt; t += str) {
+        A r = Cvt<T>::load(
+            ((const T *)((const uint8_t *)a.peer_in[0] + a.sl_b))[t]);
+#pragma unroll
+        for (int s = 1; s < NR; s++) {
+            if (s < n) {
+                r = red<A, OP>(
+                    r, Cvt<T>::load(((const T *)((const uint8_t *)
+                                                     a.peer_in[s] +
+                                                 a.sl_b))[t]));
+            }
+        }
+        T ov = Cvt<T>::store(apply_alpha<A>(r, a.alpha));
+        if (a.zc_write) {
+#pragma unroll
+            for (int s = 0; s < NR; s++) {
+                if (s < n) {
+                    ((T *)a.peer_out[s])[t] = ov;
+                }
+            }
+        } else {
+            ((T *)a.my_out)[t] = ov;
+        }
+    }
+    /* exit: every block counts on phase 1; the last arriver pushed the
+     * mirrors and stays on as this rank's gather launch: wait for the
+     * TEAM's reduces (every peer has written my dst and stopped reading
+     * my src), then phase 2 (+1, mirrors) and the host completion word */
+    if (!gated_signal_last(a, 1, a.t_sig_reduce)) {
+        return;
+    }
+    if (!gated_wait(a, 1, a.t_gather_wait)) {
+        return;
+    }
+    if (a.zc_write) {
+        gated_signal(a, 2, a.t_sig_gather, /*pub_done=*/true);
+    } else if (a.done_host && threadIdx.x == 0) {
+        __hip_atomic_store(a.done_host, a.done_seq, __ATOMIC_RELEASE,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 ucc_status_t gated_wait_only(const GatedArgs &a, hipStream_t s)
 {
     /* pure wait: one block is enough (it adds no signal counts) */
@@ -1509,6 +1817,79 @@ ucc_status_t staged_reduce(const GatedArgs &a_in, hipStream_t s)
         UCC_DT_CASE_INT(UCC_DT_UINT32, uint32_t, launch_staged_reduce)
         UCC_DT_CASE_INT(UCC_DT_INT64, int64_t, launch_staged_reduce)
         UCC_DT_CASE_INT(UCC_DT_UINT64, uint64_t, launch_staged_reduce)
+    default: return UCC_ERR_NOT_SUPPORTED;
+    }
+}
+
+template <typename T, int OP>
+static ucc_status_t launch_zc_allreduce(const GatedArgs &a, hipStream_t s)
+{
+    constexpr int VEC = VecOf<T>::value;
+    /* same depth rule and overrides as launch_staged_reduce. The kernel
+     * unrolls kMaxRanks / U peers, so an overridden depth is halved
+     * until U * nranks fits; depth 8 runs as 4 (the second pack buffer
+     * already doubles the bytes in flight). The kernel is compiled for
+     * blocks of at most 256 threads. */
+    static int ov = [] {
+        const char *e = getenv("UCC_EC_REDUCE_DEPTH");
+        return e ? atoi(e) : 0;
+    }();
+    static int thr = [] {
+        const char *e = getenv("UCC_EC_REDUCE_THREADS");
+        return e && atoi(e) == 128 ? 128 : 256;
+    }();
+    int depth = ov ? ov : (a.nranks <= 2 ? 4 : a.nranks <= 4 ? 2 : 1);
+    if (depth > 4) {
+        depth = 4;
+    }
+    while (depth > 1 && depth * a.nranks > kMaxRanks) {
+        depth /= 2;
+    }
+    int blocks = gated_grid(a), threads = thr;
+    switch (depth) {
+    case 4:
+        hipLaunchKernelGGL((k_zc_allreduce<T, OP, VEC, 4>), dim3(blocks),
+                           dim3(threads), 0, s, a);
+        break;
+    case 2:
+        hipLaunchKernelGGL((k_zc_allreduce<T, OP, VEC, 2>), dim3(blocks),
+                           dim3(threads), 0, s, a);
+        break;
+    default:
+        hipLaunchKernelGGL((k_zc_allreduce<T, OP, VEC, 1>), dim3(blocks),
+                           dim3(threads), 0, s, a);
+    }
+    return hipGetLastError() == hipSuccess ? UCC_OK : UCC_ERR_NO_RESOURCE;
+}
+
+ucc_status_t zc_allreduce(const GatedArgs &a_in, hipStream_t s)
+{
+    if (a_in.derive || a_in.nranks < 2 || a_in.nranks > kMaxRanks) {
+        return UCC_ERR_NOT_SUPPORTED; /* host-target mode only */
+    }
+    GatedArgs a = a_in;
+    if ((a.dt == UCC_DT_FLOAT32_COMPLEX || a.dt == UCC_DT_FLOAT64_COMPLEX) &&
+        (a.op == UCC_OP_SUM || a.op == UCC_OP_AVG ||
+         (int)a.op == 12)) {
+        a.dt = a.dt == UCC_DT_FLOAT32_COMPLEX ? UCC_DT_FLOAT32
+                                              : UCC_DT_FLOAT64;
+    }
+    ucc_reduction_op_t op = a.op;
+    switch (a.dt) {
+        UCC_DT_CASE_FLOAT(UCC_DT_BFLOAT16, bf16_t, launch_zc_allreduce)
+        UCC_DT_CASE_FLOAT(UCC_DT_FLOAT16, fp16_t, launch_zc_allreduce)
+        UCC_DT_CASE_FLOAT(UCC_DT_FLOAT32, float, launch_zc_allreduce)
+        UCC_DT_CASE_FLOAT(UCC_DT_FLOAT64, double, launch_zc_allreduce)
+        UCC_DT_CASE_FLOAT(UCC_DT_FLOAT8_E4M3, e4m3_t, launch_zc_allreduce)
+        UCC_DT_CASE_FLOAT(UCC_DT_FLOAT8_E5M2, e5m2_t, launch_zc_allreduce)
+        UCC_DT_CASE_INT(UCC_DT_INT8, int8_t, launch_zc_allreduce)
+        UCC_DT_CASE_INT(UCC_DT_UINT8, uint8_t, launch_zc_allreduce)
+        UCC_DT_CASE_INT(UCC_DT_INT16, int16_t, launch_zc_allreduce)
+        UCC_DT_CASE_INT(UCC_DT_UINT16, uint16_t, launch_zc_allreduce)
+        UCC_DT_CASE_INT(UCC_DT_INT32, int32_t, launch_zc_allreduce)
+        UCC_DT_CASE_INT(UCC_DT_UINT32, uint32_t, launch_zc_allreduce)
+        UCC_DT_CASE_INT(UCC_DT_INT64, int64_t, launch_zc_allreduce)
+        UCC_DT_CASE_INT(UCC_DT_UINT64, uint64_t, launch_zc_allreduce)
     default: return UCC_ERR_NOT_SUPPORTED;
     }
 }

@@ -2192,6 +2192,16 @@ class GatedCollTask final : public Cdna4Task {
                                 profiles/rocprof_kernels_r02.md */
                        : ec_hip::kGatedBlocks);
         const uint64_t B = (uint64_t)nblk;
+        /* zero-copy allreduce / reduce_scatter posted from the host:
+         * the stage signal, the reduce and the completion wait run as
+         * ONE kernel (docs/GATED_PIPELINE.md "Fused zero-copy
+         * allreduce"); derive mode keeps the three-kernel pattern its
+         * per-block launch arithmetic is built on */
+        const bool zc_fused =
+            zc_ && zc_ready_ && nfrags_ == 1 && !derive &&
+            (ct_ == UCC_COLL_TYPE_ALLREDUCE ||
+             ct_ == UCC_COLL_TYPE_REDUCE_SCATTER) &&
+            Config::instance().get_bool("TL_CDNA4", "ZC_FUSED", true);
         for (size_t f = 0; f < nfrags_; f++) {
             const uint32_t p   = (uint32_t)(f & 1);
             const size_t   off = f * gran_;
@@ -2271,6 +2281,22 @@ class GatedCollTask final : public Cdna4Task {
                 ga.t_sig_stage   = L[0][slot_][p] + Bs;
                 ga.t_sig_reduce  = L[1][slot_][p] + B;
                 ga.t_sig_gather  = L[2][slot_][p] + Bg;
+                if (zc_fused) {
+                    /* one launch on comp_s: block 0 is the stage
+                     * signal, the last-arriving block the completion
+                     * wait — same ledger as the three launches */
+                    log_path("one-kernel (k_zc_allreduce)", nblk);
+                    ga.done_host = tt_->gdone_host_ + slot_;
+                    ga.done_seq  = done_seq_;
+                    st = ec_hip::zc_allreduce(ga, comp_s);
+                    L[0][slot_][p] += Bs; /* 1 */
+                    L[1][slot_][p] += B;
+                    L[2][slot_][p] += Bg; /* 1 */
+                    break;
+                }
+                if (ga.zc_write && !derive) {
+                    log_path("three-kernel (stage/reduce/gather)", nblk);
+                }
                 {
                     ec_hip::GatedArgs gs = ga;
                     gs.nblocks           = (int)Bs;
@@ -2334,6 +2360,21 @@ class GatedCollTask final : public Cdna4Task {
                 ga.t_stage       = L[0][slot_][p] + Bs;
                 ga.t_sig_stage   = L[0][slot_][p] + Bs;
                 ga.t_sig_reduce  = L[1][slot_][p] + B;
+                if (zc_fused) {
+                    /* same kernel, zc_write = 0: my slice into my dst
+                     * only, team-reduces-done wait, no phase 2 */
+                    log_path("one-kernel (k_zc_allreduce)", nblk);
+                    ga.t_gather_wait = L[1][slot_][p] + B;
+                    ga.done_host     = tt_->gdone_host_ + slot_;
+                    ga.done_seq      = done_seq_;
+                    st = ec_hip::zc_allreduce(ga, comp_s);
+                    L[0][slot_][p] += Bs; /* 1 */
+                    L[1][slot_][p] += B;
+                    break;
+                }
+                if (zc_ && zc_ready_ && !derive) {
+                    log_path("three-kernel (stage/reduce/wait)", nblk);
+                }
                 {
                     ec_hip::GatedArgs gs = ga;
                     gs.nblocks           = (int)Bs;
@@ -2532,6 +2573,18 @@ class GatedCollTask final : public Cdna4Task {
     bool                a2av_ready_ = false; /* global max exchanged  */
     uint64_t            a2av_gsum_  = 0;     /* global send-byte sum  */
     uint64_t            done_seq_   = 0;     /* host completion seq   */
+    bool                path_logged_ = false;
+
+    /* one debug line per task naming the zero-copy launch pattern */
+    void log_path(const char *path, int nblk)
+    {
+        if (!path_logged_) {
+            path_logged_ = true;
+            ucc_debug("cdna4 gated %s: zero-copy %s path, %d blocks, "
+                      "%zu bytes", coll_type_name(ct_), path, nblk,
+                      (size_t)total_);
+        }
+    }
     int                pslot_ = -1;
     /* zero-copy persistent allreduce: peers' USER src buffers mapped
      * via HIP-IPC (handles exchanged through the scratch channel at
@@ -2590,6 +2643,9 @@ class Cdna4Tl final : public Tl {
                     "(hipMemcpyAsync) instead of gather kernels");
         cfg.declare("TL_CDNA4", "ZC_DEFRAG", "1",
                     "single-fragment zero-copy collectives (debug off)");
+        cfg.declare("TL_CDNA4", "ZC_FUSED", "1",
+                    "zero-copy allreduce/reduce_scatter as one kernel "
+                    "per post; 0 = stage/reduce/gather launches (debug)");
         cfg.declare("TL_CDNA4", "PUSH", "1",
                     "push-model gated flags; 0 = remote-poll fallback "
                     "(debug)");
