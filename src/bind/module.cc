@@ -19,6 +19,7 @@
 #include "../api/ucc.h"
 #include "../topo/topo.h"
 #include "../mc/mc.h"
+#include "../ec/ec_hip.h"
 
 namespace py = pybind11;
 
@@ -567,6 +568,8 @@ PYBIND11_MODULE(_core, m)
         (uint64_t)UCC_COLL_ARGS_FLAG_MEM_MAPPED_BUFFERS;
     m.def("dt_size", [](int dt) { return ucc_dt_size((ucc_datatype_t)dt); });
     m.def("version", []() { return std::string(ucc_get_version_string()); });
+    m.def("ec_reduce_scalar_launches",
+          []() { return ucc::ec_hip::reduce_scalar_launches(); });
     m.def("hip_device_count",
           []() { return ucc_amd_hip_device_count_c(); });
     /* raw (non-cache-hit) allocations done by the mc scratch mpool —

@@ -725,7 +725,7 @@ class HierAllreducePipeTask final : public PipelineTask {
                 ra.count   = cnt;
                 ra.dt      = dt_;
                 ra.op      = (ucc_reduction_op_t)12; /* SUM w/ alpha */
-                ra.alpha   = 1.0f / (float)team_->size;
+                ra.alpha   = 1.0 / (double)team_->size;
                 ucc_status_t rs = ec_hip::reduce(ra, nullptr);
                 if (rs != UCC_OK) {
                     return rs;
@@ -1890,7 +1890,7 @@ class HierReduceTask final : public Task {
                         ra.count   = count_;
                         ra.dt      = dt_;
                         ra.op      = (ucc_reduction_op_t)12;
-                        ra.alpha   = 1.0f / (float)team_->size;
+                        ra.alpha   = 1.0 / (double)team_->size;
                         ucc_status_t rs = ec_hip::reduce(ra, nullptr);
                         if (rs != UCC_OK) {
                             return rs;

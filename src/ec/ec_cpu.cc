@@ -107,12 +107,12 @@ uint8_t float_to_fp8e4m3(float f)
     if (std::isnan(f)) {
         return 0x7f;
     }
-    uint8_t sign = f < 0 ? 0x80 : 0;
+    uint8_t sign = std::signbit(f) ? 0x80 : 0;
     float   a    = std::fabs(f);
     if (a >= 448.0f) { /* saturate to max finite (OCP e4m3fn) */
         return sign | 0x7e;
     }
-    if (a < std::ldexp(1.0f, -9)) { /* below half of min subnormal */
+    if (a == 0.0f) {
         return sign;
     }
     int   e;
@@ -120,7 +120,8 @@ uint8_t float_to_fp8e4m3(float f)
     e -= 1;                      /* a = (2m) * 2^(e), 2m in [1,2) */
     int   exp = e + 7;
     float man;
-    if (exp <= 0) { /* subnormal */
+    if (exp <= 0) { /* subnormal, or below: 2^-10 (half the minimum
+                     * subnormal) ties to even, i.e. to zero */
         man     = a / std::ldexp(1.0f, -6) * 8.0f;
         int mi  = (int)std::nearbyint(man);
         if (mi >= 8) {
@@ -171,10 +172,10 @@ uint8_t float_to_fp8e5m2(float f)
     }
     uint8_t sign = std::signbit(f) ? 0x80 : 0;
     float   a    = std::fabs(f);
-    if (std::isinf(f) || a > 57344.0f) {
+    if (std::isinf(f)) {
         return sign | 0x7c;
     }
-    if (a < std::ldexp(1.0f, -17)) {
+    if (a == 0.0f) {
         return sign;
     }
     int   e;
@@ -193,8 +194,8 @@ uint8_t float_to_fp8e5m2(float f)
         mi = 0;
         exp++;
     }
-    if (exp >= 0x1f) {
-        return sign | 0x7c;
+    if (exp >= 0x1f) { /* finite overflow saturates to max finite */
+        return sign | 0x7b;
     }
     return sign | (uint8_t)(exp << 2) | (uint8_t)mi;
 }

@@ -29,9 +29,13 @@ struct ReduceArgs {
     uint64_t     count;
     ucc_datatype_t     dt;
     ucc_reduction_op_t op;
-    float        alpha;
+    double      alpha;
 };
 ucc_status_t reduce(const ReduceArgs &a, hipStream_t stream);
+/* launches of reduce() so far that took the element-wise kernel
+ * (k_reduce_scalar) because dst or a source is not 16-byte aligned; the
+ * tests of that kernel read it to prove that it ran */
+uint64_t reduce_scalar_launches();
 
 /* Gather-copy: dst_base+off[i] <- srcs[i], len[i] bytes, i in [0,n). */
 struct GatherArgs {
@@ -62,7 +66,7 @@ struct FusedArgs {
                                  including this launch (host-tracked)   */
     ucc_datatype_t     dt;
     ucc_reduction_op_t op;
-    float       alpha;
+    double      alpha;
     uint64_t   *error_word; /* local fine-grained word set on spin timeout */
     int         nblocks;    /* workgroups; each handles a count slice     */
     uint64_t    spin_limit; /* 0 = default kSpinLimit                     */
@@ -100,7 +104,7 @@ struct GraphFusedArgs {
     int         rank, nranks, slot;
     ucc_datatype_t     dt;
     ucc_reduction_op_t op;
-    float       alpha;
+    double      alpha;
     uint64_t   *error_word;
     int         nblocks;       /* <= kMaxGraphBlocks */
     uint64_t    parity_stride; /* bytes between parity-0 and parity-1
@@ -173,7 +177,7 @@ struct GatedArgs {
     int         rank, nranks, slot, parity;
     ucc_datatype_t     dt;
     ucc_reduction_op_t op;
-    float       alpha;
+    double      alpha;
     /* cumulative block-count targets (host-tracked). Counters are shared
      * by every gated collective type on a (slot,parity), so area-reuse
      * waits cover BOTH possible consumer phases:

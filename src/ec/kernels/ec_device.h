@@ -58,6 +58,18 @@ __device__ __forceinline__ uint16_t d_f_to_bf16(float f)
 #endif
 
 #ifdef UCC_NATIVE_FP8
+/* The reduction rule (docs/USER_GUIDE.md, "Reduction numerics") saturates
+ * FINITE overflow to +-max. The pk converts are not relied on for that
+ * (ROCm's own fp8 header clamps in front of them too): clamp in f32
+ * first; NaN and +-inf (exponent field all ones) pass through untouched. */
+__device__ __forceinline__ float d_satfinite(float f, float big)
+{
+    return (__float_as_uint(f) & 0x7f800000u) == 0x7f800000u
+               ? f
+               : __builtin_amdgcn_fmed3f(f, big, -big);
+}
+constexpr float kE4m3Max = 448.0f;
+constexpr float kE5m2Max = 57344.0f;
 /* paired converts: one VOP handles 2 elements (v_cvt_pk_f32_fp8 /
  * v_cvt_pk_fp8_f32) — halves the VALU cost of the fp8 reduce, which is
  * 2x the elements per byte of bf16 */
@@ -72,6 +84,8 @@ __device__ __forceinline__ void d_e4m3x2_to_f(uint8_t lo, uint8_t hi,
 __device__ __forceinline__ void d_f_to_e4m3x2(float a, float b,
                                               uint8_t &lo, uint8_t &hi)
 {
+    a = d_satfinite(a, kE4m3Max);
+    b = d_satfinite(b, kE4m3Max);
     int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
     lo    = (uint8_t)w;
     hi    = (uint8_t)(w >> 8);
@@ -87,6 +101,8 @@ __device__ __forceinline__ void d_e5m2x2_to_f(uint8_t lo, uint8_t hi,
 __device__ __forceinline__ void d_f_to_e5m2x2(float a, float b,
                                               uint8_t &lo, uint8_t &hi)
 {
+    a = d_satfinite(a, kE5m2Max);
+    b = d_satfinite(b, kE5m2Max);
     int w = __builtin_amdgcn_cvt_pk_bf8_f32(a, b, 0, false);
     lo    = (uint8_t)w;
     hi    = (uint8_t)(w >> 8);
@@ -109,7 +125,11 @@ __device__ __forceinline__ void d_e4m3x4_to_f(uint32_t w, float &a,
 __device__ __forceinline__ uint32_t d_f_to_e4m3x4(float a, float b,
                                                   float c, float d)
 {
+    a = d_satfinite(a, kE4m3Max);
+    b = d_satfinite(b, kE4m3Max);
     int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+    c = d_satfinite(c, kE4m3Max);
+    d = d_satfinite(d, kE4m3Max);
     w     = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
     return (uint32_t)w;
 }
@@ -127,7 +147,11 @@ __device__ __forceinline__ void d_e5m2x4_to_f(uint32_t w, float &a,
 __device__ __forceinline__ uint32_t d_f_to_e5m2x4(float a, float b,
                                                   float c, float d)
 {
+    a = d_satfinite(a, kE5m2Max);
+    b = d_satfinite(b, kE5m2Max);
     int w = __builtin_amdgcn_cvt_pk_bf8_f32(a, b, 0, false);
+    c = d_satfinite(c, kE5m2Max);
+    d = d_satfinite(d, kE5m2Max);
     w     = __builtin_amdgcn_cvt_pk_bf8_f32(c, d, w, true);
     return (uint32_t)w;
 }
@@ -137,6 +161,7 @@ __device__ __forceinline__ float d_e4m3_to_f(uint8_t v)
 }
 __device__ __forceinline__ uint8_t d_f_to_e4m3(float f)
 {
+    f = d_satfinite(f, kE4m3Max);
     return (uint8_t)__builtin_amdgcn_cvt_pk_fp8_f32(f, f, 0, false);
 }
 __device__ __forceinline__ float d_e5m2_to_f(uint8_t v)
@@ -145,6 +170,7 @@ __device__ __forceinline__ float d_e5m2_to_f(uint8_t v)
 }
 __device__ __forceinline__ uint8_t d_f_to_e5m2(float f)
 {
+    f = d_satfinite(f, kE5m2Max);
     return (uint8_t)__builtin_amdgcn_cvt_pk_bf8_f32(f, f, 0, false);
 }
 #else
@@ -167,12 +193,12 @@ __device__ __forceinline__ uint8_t d_f_to_e4m3(float f)
     if (isnan(f)) {
         return 0x7f;
     }
-    uint8_t sign = f < 0.0f ? 0x80 : 0;
+    uint8_t sign = signbit(f) ? 0x80 : 0;
     float   a    = fabsf(f);
     if (a >= 448.0f) {
         return sign | 0x7e;
     }
-    if (a < 0.001953125f) { /* 2^-9 */
+    if (a == 0.0f) {
         return sign;
     }
     int   e;
@@ -217,10 +243,10 @@ __device__ __forceinline__ uint8_t d_f_to_e5m2(float f)
     }
     uint8_t sign = signbit(f) ? 0x80 : 0;
     float   a    = fabsf(f);
-    if (isinf(f) || a > 57344.0f) {
+    if (isinf(f)) {
         return sign | 0x7c;
     }
-    if (a < exp2f(-17.0f)) {
+    if (a == 0.0f) {
         return sign;
     }
     int   e;
@@ -238,8 +264,8 @@ __device__ __forceinline__ uint8_t d_f_to_e5m2(float f)
         mi = 0;
         exp++;
     }
-    if (exp >= 0x1f) {
-        return sign | 0x7c;
+    if (exp >= 0x1f) { /* finite overflow saturates to max finite */
+        return sign | 0x7b;
     }
     return sign | (uint8_t)(exp << 2) | (uint8_t)mi;
 }
@@ -343,10 +369,18 @@ __device__ __forceinline__ A red(A a, A b)
 }
 
 template <typename A>
-__device__ __forceinline__ A apply_alpha(A v, float alpha)
+__device__ __forceinline__ A apply_alpha(A v, double alpha)
 {
     if constexpr (std::is_floating_point<A>::value) {
-        return (A)(v * (A)alpha);
+        /* The product is rounded to A HERE; the store converts it once
+         * more. The empty asm pins that: without it instruction selection
+         * folds this multiply into the fp16 convert
+         * (v_fma_mixlo_f16 v, alpha, 0), which rounds once from the exact
+         * product and turns -0 into +0 (-0 * alpha + 0). It is selection,
+         * not contraction: `#pragma clang fp contract(off)` leaves it. */
+        A p = v * (A)alpha;
+        asm("" : "+v"(p));
+        return p;
     } else {
         (void)alpha;
         return v;
@@ -473,7 +507,7 @@ __device__ __forceinline__ void vaccum(A (&r)[VEC], const P &x)
 }
 template <typename T, int OP, int VEC, typename A, typename P>
 __device__ __forceinline__ void vstore(P &o, const A (&r)[VEC],
-                                       float alpha)
+                                       double alpha)
 {
     if constexpr (is_fp8_v<T> && std::is_same<A, float>::value &&
                   VEC % 4 == 0) {
@@ -502,7 +536,7 @@ __device__ __forceinline__ void vstore(P &o, const A (&r)[VEC],
 template <typename T, int OP, int VEC, int N>
 __device__ __forceinline__ Pack<T, OP, VEC>
 reduce_pack(const void *const (&srcs)[N], uint64_t off, int n, uint64_t i,
-            float alpha)
+            double alpha)
 {
     using A = typename Cvt<T>::A;
     using P = Pack<T, OP, VEC>;
@@ -521,7 +555,7 @@ reduce_pack(const void *const (&srcs)[N], uint64_t off, int n, uint64_t i,
 template <typename T, int OP, int N>
 __device__ __forceinline__ T
 reduce_elem(const void *const (&srcs)[N], uint64_t off, int n, uint64_t t,
-            float alpha)
+            double alpha)
 {
     using A = typename Cvt<T>::A;
     A r = Cvt<T>::load(((const T *)((const uint8_t *)srcs[0] + off))[t]);
@@ -538,7 +572,7 @@ reduce_elem(const void *const (&srcs)[N], uint64_t off, int n, uint64_t t,
 template <typename T, int OP, int VEC, int N>
 __device__ __forceinline__ void
 reduce_range(void *dst, const void *const (&srcs)[N], uint64_t off, int n,
-             uint64_t count, float alpha)
+             uint64_t count, double alpha)
 {
     const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t str = (uint64_t)gridDim.x * blockDim.x;

@@ -2,6 +2,8 @@
  * and the dtype/op support queries (answered from the dispatch table). */
 #include "ec_device.h"
 
+#include <atomic>
+
 namespace ucc {
 namespace ec_hip {
 
@@ -61,6 +63,10 @@ __global__ void k_gather_copy(GatherArgs a)
 /* ----------------------------------------------------------- launchers */
 static bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
 
+static std::atomic<uint64_t> g_scalar_launches{0};
+
+uint64_t reduce_scalar_launches() { return g_scalar_launches.load(); }
+
 template <typename T, int OP> struct LaunchReduce {
     static ucc_status_t run(const ReduceArgs &a, hipStream_t s)
     {
@@ -80,6 +86,7 @@ template <typename T, int OP> struct LaunchReduce {
             hipLaunchKernelGGL((k_reduce<T, OP, VEC>), dim3(blocks),
                                dim3(threads), 0, s, a);
         } else {
+            g_scalar_launches.fetch_add(1, std::memory_order_relaxed);
             hipLaunchKernelGGL((k_reduce_scalar<T, OP>), dim3(blocks),
                                dim3(threads), 0, s, a);
         }

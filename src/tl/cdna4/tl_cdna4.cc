@@ -572,7 +572,7 @@ class FusedAllreduceTask final : public Cdna4Task {
             fa.count   = a_.dst.info.count;
             fa.dt      = a_.dst.info.datatype;
             fa.op      = a_.op == UCC_OP_AVG ? UCC_OP_SUM : a_.op;
-            fa.alpha   = a_.op == UCC_OP_AVG ? 1.0f / (float)n_ : 1.0f;
+            fa.alpha   = a_.op == UCC_OP_AVG ? 1.0 / (double)n_ : 1.0;
             if (a_.op == UCC_OP_AVG) {
                 fa.op = (ucc_reduction_op_t)12; /* SUM+alpha path */
             }
@@ -656,7 +656,7 @@ class FusedAllreduceTask final : public Cdna4Task {
         ga.count   = a_.dst.info.count;
         ga.dt      = a_.dst.info.datatype;
         ga.op      = a_.op == UCC_OP_AVG ? (ucc_reduction_op_t)12 : a_.op;
-        ga.alpha   = a_.op == UCC_OP_AVG ? 1.0f / (float)n_ : 1.0f;
+        ga.alpha   = a_.op == UCC_OP_AVG ? 1.0 / (double)n_ : 1.0;
         ga.my_scratch = tt_->area(me_, (uint32_t)pslot_, 0, 0);
         for (uint32_t r = 0; r < n_; r++) {
             ga.peer_scratch[r] = tt_->area(r, (uint32_t)pslot_, 0, 0);
@@ -713,11 +713,11 @@ class StagedTask final : public Cdna4Task {
         const bool inplace = a_.flags & UCC_COLL_ARGS_FLAG_IN_PLACE;
         ct_     = a_.coll_type;
         steps_  = ct_ == UCC_COLL_TYPE_ALLREDUCE ? 3 : 2;
-        alpha_  = 1.0f;
+        alpha_  = 1.0;
         op_     = a_.op;
         if (op_ == UCC_OP_AVG) {
             op_    = (ucc_reduction_op_t)12;
-            alpha_ = 1.0f / (float)n_;
+            alpha_ = 1.0 / (double)n_;
         }
         cnt_.assign(n_, 0);
         dsp_.assign(n_, 0);
@@ -1386,7 +1386,7 @@ class StagedTask final : public Cdna4Task {
     ucc_datatype_t  dt_   = UCC_DT_INT8;
     size_t          dtsz_ = 1;
     ucc_reduction_op_t op_ = UCC_OP_SUM;
-    float           alpha_ = 1.0f;
+    double          alpha_ = 1.0;
     size_t          total_ = 0, nfrags_ = 0;
     size_t          gran_ = 0, cell_ = 0;
     std::vector<size_t> cnt_, dsp_, rcnt_, rdsp_;
@@ -1503,12 +1503,12 @@ class GatedCollTask final : public Cdna4Task {
         const bool inplace = a_.flags & UCC_COLL_ARGS_FLAG_IN_PLACE;
         ct_     = a_.coll_type;
         op_     = a_.op;
-        alpha_  = 1.0f;
+        alpha_  = 1.0;
         gran_   = tt_->cfg_.chunk;
         cell_   = (tt_->cfg_.chunk / n_) & ~(size_t)255;
         if (op_ == UCC_OP_AVG) {
             op_    = (ucc_reduction_op_t)12;
-            alpha_ = 1.0f / (float)n_;
+            alpha_ = 1.0 / (double)n_;
         }
         switch (ct_) {
         case UCC_COLL_TYPE_ALLREDUCE:
@@ -2563,7 +2563,7 @@ class GatedCollTask final : public Cdna4Task {
     ucc_coll_type_t    ct_    = UCC_COLL_TYPE_ALLREDUCE;
     ucc_datatype_t     dt_    = UCC_DT_FLOAT32;
     ucc_reduction_op_t op_    = UCC_OP_SUM;
-    float              alpha_ = 1.0f;
+    double             alpha_ = 1.0;
     size_t             dtsz_ = 4, total_ = 0, nfrags_ = 0;
     size_t             gran_ = 0, cell_ = 0, out_b_ = 0;
     const uint8_t     *sbuf_ = nullptr;

@@ -26,6 +26,9 @@ def job(request):
 
 
 def _run_device(job, coll, per_rank):
+    # the buffers were filled on torch's stream, the collective runs on the
+    # library's own streams: finish the fills before it may touch them
+    torch.cuda.synchronize()
     reqs = job.coll(coll, per_rank)
     job.run(reqs)
     torch.cuda.synchronize()
