@@ -40,7 +40,8 @@ SHLIB  := $(BUILD)/libucc_amd.so
 
 PERFTEST := build/ucc_perftest
 INFO     := build/ucc_info
-NTESTS   := build/test_generic_dt build/test_obj_size build/test_mt
+NTESTS   := build/test_generic_dt build/test_obj_size build/test_mt \
+            build/test_p2p_mbox
 
 all: $(MODULE) $(SHLIB) $(PERFTEST) $(INFO) $(NTESTS)
 
@@ -56,6 +57,10 @@ build/test_obj_size: $(BUILD)/tests/test_obj_size.o $(LIB_OBJS)
 
 build/test_mt: $(BUILD)/tests/test_mt.o $(LIB_OBJS)
 	$(HIPCC) $^ -o $@ -lrt -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+
+# host-only: the p2p mailbox header and nothing else of the library
+build/test_p2p_mbox: $(BUILD)/tests/test_p2p_mbox.o
+	$(HIPCC) $^ -o $@ -lrt
 
 $(BUILD)/tools/%.o: tools/%.cc tools/shm_oob.h
 	@mkdir -p $(dir $@)
@@ -129,8 +134,13 @@ build/asan_generic_dt: $(BUILD)/asan/tests/test_generic_dt.o $(ASAN_OBJS)
 build/asan_obj_size: $(BUILD)/asan/tests/test_obj_size.o $(ASAN_OBJS)
 	$(HIPCC) -fsanitize=address $^ -o $@ -lrt -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
+build/asan_p2p_mbox: $(BUILD)/asan/tests/test_p2p_mbox.o
+	$(HIPCC) -fsanitize=address $^ -o $@ -lrt
+
 .PHONY: asan
-asan: build/asan_generic_dt build/asan_obj_size build/asan_perftest
+asan: build/asan_generic_dt build/asan_obj_size build/asan_perftest \
+      build/asan_p2p_mbox
+	ASAN_OPTIONS=detect_leaks=1 ./build/asan_p2p_mbox
 	ASAN_OPTIONS=detect_leaks=1 ./build/asan_obj_size
 	ASAN_OPTIONS=detect_leaks=1 ./build/asan_generic_dt
 	for cl in allreduce bcast alltoall alltoallv reduce_scatter barrier; do \

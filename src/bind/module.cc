@@ -10,11 +10,14 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <chrono>
 #include <cstring>
 #include <map>
 #include <memory>
 #include <mutex>
 #include <vector>
+
+#include <hip/hip_runtime.h>
 
 #include "../api/ucc.h"
 #include "../topo/topo.h"
@@ -570,6 +573,51 @@ PYBIND11_MODULE(_core, m)
     m.def("version", []() { return std::string(ucc_get_version_string()); });
     m.def("ec_reduce_scalar_launches",
           []() { return ucc::ec_hip::reduce_scalar_launches(); });
+    /* kernel unit-test hook: one k_p2p_pull launch on the null stream,
+     * in-process; returns the grid size once the completion word shows
+     * this launch (blocks = 0: the size-derived auto grid) */
+    m.def(
+        "ec_p2p_pull",
+        [](uintptr_t dst, uintptr_t src, uint64_t nbytes, int blocks) {
+            static uint64_t *cnt = nullptr, *done = nullptr;
+            static uint64_t  cum = 0, seq = 0;
+            if (!cnt) {
+                uint64_t *c = nullptr, *d = nullptr;
+                if (hipMalloc((void **)&c, 64) != hipSuccess ||
+                    hipMemset(c, 0, 64) != hipSuccess ||
+                    hipHostMalloc((void **)&d, 64, hipHostMallocDefault) !=
+                        hipSuccess) {
+                    throw std::runtime_error("ec_p2p_pull: no memory");
+                }
+                *d   = 0;
+                cnt  = c;
+                done = d;
+            }
+            ucc::ec_hip::P2pPullArgs a{};
+            a.dst     = (void *)dst;
+            a.src     = (const void *)src;
+            a.len     = nbytes;
+            a.nblocks = blocks > 0 ? blocks
+                                   : ucc::ec_hip::p2p_auto_blocks(nbytes);
+            a.arrive_cnt  = cnt;
+            a.done_host   = done;
+            a.done_target = cum + (uint64_t)a.nblocks;
+            a.done_seq    = seq + 1;
+            check(ucc::ec_hip::p2p_pull(a, nullptr), "p2p_pull");
+            cum = a.done_target;
+            seq = a.done_seq;
+            const auto t0 = std::chrono::steady_clock::now();
+            while (__atomic_load_n(done, __ATOMIC_ACQUIRE) < seq) {
+                if (std::chrono::steady_clock::now() - t0 >
+                    std::chrono::seconds(20)) {
+                    throw std::runtime_error(
+                        "ec_p2p_pull: completion word not written");
+                }
+            }
+            return a.nblocks;
+        },
+        py::arg("dst"), py::arg("src"), py::arg("nbytes"),
+        py::arg("blocks") = 0);
     m.def("hip_device_count",
           []() { return ucc_amd_hip_device_count_c(); });
     /* raw (non-cache-hit) allocations done by the mc scratch mpool —

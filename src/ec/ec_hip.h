@@ -249,6 +249,39 @@ ucc_status_t zc_allreduce(const GatedArgs &a, hipStream_t s);
 ucc_status_t gated_wait_only(const GatedArgs &a, hipStream_t s);
 ucc_status_t gated_done(const GatedArgs &a, hipStream_t s);
 
+/* ------------------------------------------------------------------------
+ * p2p pull (device active-set bcast): dst <- src, len bytes, src usually a
+ * peer mapping. src and dst alignment are independent. The kernel never
+ * waits on anything; the host gates the launch.
+ *
+ * Completion follows FusedArgs.done_host: every block adds 1 to the
+ * device-scope counter *arrive_cnt, which is never reset; the block whose
+ * add reaches done_target (host-tracked: the sum of nblocks over every
+ * launch on this counter so far, this one included) release-stores
+ * done_seq to the host-pinned word done_host. Launches that share a
+ * counter must be ordered on one stream. The counter is an allocation of
+ * the caller's own, apart from the flags buffer laid out above.
+ * len == 0 is legal: the kernel then only publishes completion. */
+constexpr int      kP2pMaxBlocks  = 1024; /* bound for the blocks knob   */
+/* auto grid: one block per kP2pBlockBytes (four 4-deep batches of 256
+ * lanes x 16 B), capped. Both values come from the measured block-count
+ * sweep in profiles/p2p_active_set.md: 16 blocks were fastest at 1 MiB,
+ * 64 at 64 MiB. */
+constexpr uint64_t kP2pBlockBytes    = 65536;
+constexpr int      kP2pAutoMaxBlocks = 64;
+struct P2pPullArgs {
+    void       *dst;
+    const void *src;
+    uint64_t    len;
+    uint64_t   *arrive_cnt;
+    uint64_t    done_target;
+    uint64_t   *done_host;
+    uint64_t    done_seq;
+    int         nblocks; /* 1..kP2pMaxBlocks */
+};
+int          p2p_auto_blocks(uint64_t len);
+ucc_status_t p2p_pull(const P2pPullArgs &a, hipStream_t stream);
+
 } // namespace ec_hip
 } // namespace ucc
 

@@ -34,6 +34,7 @@
 #include "../../topo/topo.h"
 #include "../../mc/mc.h"
 #include "../shm/slot_seg.h"
+#include "p2p_mbox.h"
 
 namespace ucc {
 namespace {
@@ -94,6 +95,9 @@ struct Cdna4Cfg {
     int      gated_blocks; /* gated kernel grid size (team constant)  */
     bool     ce_alltoall;  /* SDMA copy-engine alltoall data path     */
     size_t   ce_alltoall_min; /* min total msg bytes for the CE path  */
+    bool     p2p;        /* device active-set bcast (p2p send/recv)      */
+    uint32_t p2p_depth;  /* mailbox ring depth, power of two <= 64       */
+    int      p2p_blocks; /* pull kernel grid size; 0 = size-derived      */
 };
 
 class Cdna4Tl;
@@ -171,6 +175,14 @@ class Cdna4TlTeam final : public TlTeam {
         if (init_st_ == UCC_OK && team->rank == 0) {
             init_st_ = seg_.create(seg_name_, team->size, cfg_.nslots, 0);
         }
+        mbox_name_ = seg_name_ + "-p2p";
+        if (init_st_ == UCC_OK && cfg_.p2p && team->rank == 0) {
+            init_st_ = mbox_.create(mbox_name_, team->size, cfg_.p2p_depth);
+        }
+        p2p_send_seq_.assign(team->size, 0);
+        p2p_recv_seq_.assign(team->size, 0);
+        p2p_recv_taken_.assign(team->size, 0);
+        p2p_send_read_.assign(team->size, 0);
     }
 
     /* team-lifetime IPC import cache: user-buffer handles opened for
@@ -247,6 +259,9 @@ class Cdna4TlTeam final : public TlTeam {
         if (err_host_) {
             HIPWARN(hipHostFree(err_host_));
         }
+        if (p2p_cnt_) {
+            HIPWARN(hipFree(p2p_cnt_));
+        }
     }
 
     ucc_status_t local_init()
@@ -270,11 +285,16 @@ class Cdna4TlTeam final : public TlTeam {
             HIPCHK(hipMalloc((void **)&flags_, ec_hip::kFlagsBytes));
         }
         HIPCHK(hipMemset(flags_, 0, ec_hip::kFlagsBytes));
-        HIPCHK(hipHostMalloc((void **)&err_host_, 192,
+        HIPCHK(hipHostMalloc((void **)&err_host_, 256,
                              hipHostMallocDefault));
-        memset((void *)err_host_, 0, 192);
+        memset((void *)err_host_, 0, 256);
         done_host_  = err_host_ + 8;  /* [8..15]: per-slot fused flags */
         gdone_host_ = err_host_ + 16; /* [16..23]: per-slot gated flags */
+        p2p_done_host_ = err_host_ + 24; /* [24]: p2p pull launch seq   */
+        /* p2p pull arrival counter: an allocation of its own, clear of
+         * the flags_ layout documented in ec_hip.h */
+        HIPCHK(hipMalloc((void **)&p2p_cnt_, 64));
+        HIPCHK(hipMemset(p2p_cnt_, 0, 64));
         gdone_seq_.assign(ec_hip::kGatedSlots, 0);
         HIPCHK(hipDeviceSynchronize());
         return UCC_OK;
@@ -392,7 +412,16 @@ class Cdna4TlTeam final : public TlTeam {
             }
             attached_ = true;
         }
-        return seg_.ready() ? UCC_OK : UCC_INPROGRESS;
+        if (cfg_.p2p && !mbox_.attached()) {
+            ucc_status_t st =
+                mbox_.attach(mbox_name_, team_->size, cfg_.p2p_depth);
+            if (st != UCC_OK) {
+                return st; /* INPROGRESS: creator not there yet */
+            }
+        }
+        return seg_.ready() && (!cfg_.p2p || mbox_.ready())
+                   ? UCC_OK
+                   : UCC_INPROGRESS;
     }
 
     void get_scores(Team *team, ScoreMap &map) override;
@@ -471,6 +500,20 @@ class Cdna4TlTeam final : public TlTeam {
     std::vector<PeerRes> peers_;
     ucc_status_t init_st_ = UCC_OK;
     bool         attached_ = false;
+    /* device active-set bcast (ActiveSetBcastTask): per-pair mailbox and
+     * this rank's host state of its channels, all under p2p_mu_. None of
+     * it touches seq_, the slots or gated_launch_. */
+    P2pMbox      mbox_;
+    std::string  mbox_name_;
+    std::mutex   p2p_mu_;
+    std::vector<uint64_t> p2p_send_seq_;   /* [member]: last seq taken   */
+    std::vector<uint64_t> p2p_recv_seq_;   /* [root]: last seq taken     */
+    std::vector<uint64_t> p2p_recv_taken_; /* [root]: last seq consumed  */
+    std::vector<uint64_t> p2p_send_read_;  /* [member]: last ack read    */
+    uint64_t    *p2p_cnt_       = nullptr; /* device arrival counter     */
+    uint64_t    *p2p_done_host_ = nullptr; /* host-pinned launch seq     */
+    uint64_t     p2p_blocks_cum_ = 0;      /* blocks launched so far     */
+    uint64_t     p2p_launches_   = 0;
 };
 
 /* -------------------------------------------------------------- tasks  */
@@ -2607,6 +2650,285 @@ class GatedCollTask final : public Cdna4Task {
     }
 };
 
+/* Device active-set bcast: a transfer of one device buffer from `root` to
+ * the other members of the strided rank subset {start, stride, size}. A
+ * 2-member set with the sender as root is a send/recv (reference: tl/ucp
+ * active-set bcast, the p2p that pipeline stages ride on).
+ *
+ * Non-members post nothing, so this task takes no part in the team-wide
+ * post order: no begin_use(), no seq_, no rotating or persistent slot, no
+ * gated_launch_. Its control channel is the per-pair mailbox
+ * (p2p_mbox.h): the root publishes one descriptor (length, tag, IPC handle
+ * of the source) per other member and launches nothing; each member waits
+ * ON THE HOST for its descriptor, then pulls the bytes with one
+ * k_p2p_pull launch, polls the host-pinned completion word and acks. The
+ * kernel never waits, so several ranks of one process on one hardware
+ * queue are safe and a dead peer cannot hang the device.
+ *
+ * Ordering: on one ordered pair transfers match in post order
+ * (non-overtaking); different pairs are independent. Tags are verified,
+ * not searched for. Host-post semantics: the source must be complete when
+ * the root posts. */
+class ActiveSetBcastTask final : public Cdna4Task {
+  public:
+    using Cdna4Task::Cdna4Task;
+
+    ucc_status_t post() override
+    {
+        me_    = tt_->team_->rank;
+        n_     = tt_->team_->size;
+        bytes_ = a_.src.info.count * ucc_dt_size(a_.src.info.datatype);
+        root_  = (uint32_t)a_.root;
+        /* member list: tl/tcp's arithmetic */
+        bool me_in = false, root_in = false;
+        std::vector<uint32_t> set;
+        for (int64_t i = 0; i < (int64_t)a_.active_set.size; i++) {
+            uint32_t r = (uint32_t)(((a_.active_set.start +
+                                      i * a_.active_set.stride) %
+                                         (int64_t)n_ +
+                                     (int64_t)n_) %
+                                    (int64_t)n_);
+            me_in |= r == me_;
+            root_in |= r == root_;
+            bool dup = false;
+            for (uint32_t s : set) {
+                dup |= s == r;
+            }
+            if (!dup) {
+                set.push_back(r);
+            }
+        }
+        if (!me_in || !root_in || a_.root >= n_) {
+            return UCC_ERR_INVALID_PARAM; /* caller or root not in the set */
+        }
+        std::lock_guard<std::mutex> g(tt_->p2p_mu_);
+        dsts_.clear();
+        if (me_ == root_) {
+            for (uint32_t r : set) {
+                if (r != me_) {
+                    dsts_.push_back(Dst{r, ++tt_->p2p_send_seq_[r], false,
+                                        false});
+                }
+            }
+            if (!exported_) {
+                export_src();
+            }
+        } else {
+            seq_ = ++tt_->p2p_recv_seq_[root_];
+        }
+        phase_  = 0;
+        result_ = UCC_OK;
+        status  = UCC_INPROGRESS;
+        return step();
+    }
+
+    ucc_status_t progress() override
+    {
+        std::lock_guard<std::mutex> g(tt_->p2p_mu_);
+        return step();
+    }
+
+  private:
+    struct Dst {
+        uint32_t rank;
+        uint64_t seq;
+        bool     published, acked;
+    };
+
+    /* root: IPC handle of the source allocation, once per request. Only
+     * needed when a member lives in another process. A failure travels in
+     * the descriptor so that the member fails too instead of waiting. */
+    void export_src()
+    {
+        exported_ = true;
+        tmpl_     = P2pDesc{};
+        tmpl_.len     = bytes_;
+        tmpl_.raw_ptr = (uint64_t)(uintptr_t)a_.src.info.buffer;
+        tmpl_.pid     = (int32_t)getpid();
+        tmpl_.has_tag = (a_.mask & UCC_COLL_ARGS_FIELD_TAG) ? 1 : 0;
+        tmpl_.tag     = tmpl_.has_tag ? a_.tag : 0;
+        bool remote = false;
+        for (auto &d : dsts_) {
+            remote |= tt_->team_->procs[d.rank].pid != tmpl_.pid;
+        }
+        if (!remote || bytes_ == 0) {
+            return;
+        }
+        uint64_t moff = 0;
+        if ((a_.mask & UCC_COLL_ARGS_FIELD_MEM_MAP_SRC_MEMH) &&
+            a_.src_memh &&
+            ucc_memh_lookup(a_.src_memh, a_.src.info.buffer, bytes_,
+                            tmpl_.handle, &moff)) {
+            g_memh_uses.fetch_add(1, std::memory_order_relaxed);
+            tmpl_.base_off   = moff;
+            tmpl_.has_handle = 1;
+            return;
+        }
+        hipDeviceptr_t    base  = nullptr;
+        size_t            bsize = 0;
+        hipIpcMemHandle_t h;
+        static_assert(sizeof(h) == sizeof(tmpl_.handle), "IPC handle size");
+        if (hipMemGetAddressRange(&base, &bsize,
+                                  (hipDeviceptr_t)a_.src.info.buffer) !=
+                hipSuccess ||
+            hipIpcGetMemHandle(&h, (void *)base) != hipSuccess) {
+            (void)hipGetLastError();
+            ucc_error("active-set bcast: cannot export source %p for IPC",
+                      a_.src.info.buffer);
+            tmpl_.status = (int32_t)UCC_ERR_NO_RESOURCE;
+            return;
+        }
+        memcpy(tmpl_.handle, &h, sizeof(h));
+        tmpl_.base_off =
+            (uint64_t)((uintptr_t)a_.src.info.buffer - (uintptr_t)base);
+        tmpl_.has_handle = 1;
+    }
+
+    ucc_status_t step() { return me_ == root_ ? step_root() : step_member(); }
+
+    /* root: publish in channel order (ring full: retry from progress),
+     * then collect the acks; first error status wins */
+    ucc_status_t step_root()
+    {
+        P2pMbox &mb   = tt_->mbox_;
+        bool     done = true;
+        for (auto &d : dsts_) {
+            if (!d.published) {
+                /* the ack status slot of seq - D is rewritten once seq is
+                 * acked: post only after its owner has read it */
+                if (!mb.can_post(me_, d.rank, d.seq) ||
+                    d.seq - tt_->p2p_send_read_[d.rank] > mb.depth()) {
+                    done = false;
+                    continue;
+                }
+                P2pDesc desc = tmpl_;
+                desc.seq     = d.seq;
+                mb.post(me_, d.rank, desc);
+                d.published = true;
+            }
+            if (!d.acked) {
+                int32_t st = 0;
+                if (tt_->p2p_send_read_[d.rank] + 1 != d.seq ||
+                    !mb.ack_of(me_, d.rank, d.seq, &st)) {
+                    done = false; /* acks are read in channel order */
+                    continue;
+                }
+                tt_->p2p_send_read_[d.rank] = d.seq;
+                d.acked = true;
+                if (st != 0 && result_ == UCC_OK) {
+                    result_ = (ucc_status_t)st;
+                }
+            }
+        }
+        if (!done) {
+            return UCC_INPROGRESS;
+        }
+        if (tmpl_.status != 0 && result_ == UCC_OK) {
+            result_ = (ucc_status_t)tmpl_.status;
+        }
+        return result_;
+    }
+
+    /* member: 0 wait for my descriptor and launch, 1 poll the completion
+     * word, 2 ack in channel order */
+    ucc_status_t step_member()
+    {
+        P2pMbox &mb = tt_->mbox_;
+        if (phase_ == 0) {
+            if (tt_->p2p_recv_taken_[root_] + 1 != seq_) {
+                return UCC_INPROGRESS; /* an earlier recv goes first */
+            }
+            const P2pDesc *d = mb.peek(root_, me_, seq_);
+            if (!d) {
+                return UCC_INPROGRESS;
+            }
+            tt_->p2p_recv_taken_[root_] = seq_; /* consumed either way */
+            const bool has_tag = a_.mask & UCC_COLL_ARGS_FIELD_TAG;
+            if (d->status != 0) {
+                ucc_error("active-set bcast from rank %u: the root could "
+                          "not export its source", root_);
+                result_ = (ucc_status_t)d->status;
+            } else if (has_tag && d->has_tag && d->tag != a_.tag) {
+                ucc_error("active-set bcast from rank %u: tag mismatch, "
+                          "root posted %u, this rank %u", root_,
+                          (unsigned)d->tag, (unsigned)a_.tag);
+                result_ = UCC_ERR_INVALID_PARAM;
+            } else if (d->len != bytes_) {
+                ucc_error("active-set bcast from rank %u: length mismatch, "
+                          "root posted %llu bytes, this rank %llu", root_,
+                          (unsigned long long)d->len,
+                          (unsigned long long)bytes_);
+                result_ = UCC_ERR_INVALID_PARAM;
+            } else {
+                result_ = launch_pull(*d);
+            }
+            phase_ = result_ == UCC_OK ? 1 : 2;
+        }
+        if (phase_ == 1) {
+            if (__atomic_load_n(tt_->p2p_done_host_, __ATOMIC_ACQUIRE) <
+                launch_) {
+                return UCC_INPROGRESS;
+            }
+            phase_ = 2;
+        }
+        if (!mb.can_ack(root_, me_, seq_)) {
+            return UCC_INPROGRESS;
+        }
+        mb.ack(root_, me_, seq_, (int32_t)result_);
+        return result_;
+    }
+
+    ucc_status_t launch_pull(const P2pDesc &d)
+    {
+        const uint8_t *src = nullptr;
+        if (d.pid == (int32_t)getpid()) {
+            src = (const uint8_t *)(uintptr_t)d.raw_ptr; /* in-process jig */
+        } else if (bytes_ > 0) {
+            if (!d.has_handle) {
+                return UCC_ERR_NO_RESOURCE;
+            }
+            hipIpcMemHandle_t h;
+            memcpy(&h, d.handle, sizeof(h));
+            void *m =
+                tt_->ipc_open_cached(d.pid, d.raw_ptr - d.base_off, h);
+            if (!m) {
+                ucc_error("active-set bcast from rank %u: IPC open of the "
+                          "source failed", root_);
+                return UCC_ERR_NO_RESOURCE;
+            }
+            src = (const uint8_t *)m + d.base_off;
+        }
+        ec_hip::P2pPullArgs pa{};
+        pa.dst     = a_.src.info.buffer;
+        pa.src     = src;
+        pa.len     = bytes_;
+        pa.nblocks = tt_->cfg_.p2p_blocks > 0
+                         ? tt_->cfg_.p2p_blocks
+                         : ec_hip::p2p_auto_blocks(bytes_);
+        pa.arrive_cnt  = tt_->p2p_cnt_;
+        pa.done_host   = tt_->p2p_done_host_;
+        pa.done_target = tt_->p2p_blocks_cum_ + (uint64_t)pa.nblocks;
+        pa.done_seq    = tt_->p2p_launches_ + 1;
+        ucc_status_t st = ec_hip::p2p_pull(pa, comp());
+        if (st != UCC_OK) {
+            return st;
+        }
+        tt_->p2p_blocks_cum_ = pa.done_target;
+        tt_->p2p_launches_   = pa.done_seq;
+        launch_              = pa.done_seq;
+        return UCC_OK;
+    }
+
+    size_t           bytes_ = 0;
+    uint32_t         root_  = 0;
+    uint64_t         seq_   = 0; /* member: my seq on channel root->me */
+    uint64_t         launch_ = 0;
+    ucc_status_t     result_ = UCC_OK;
+    std::vector<Dst> dsts_;      /* root: one entry per other member   */
+    P2pDesc          tmpl_{};
+    bool             exported_ = false;
+};
+
 /* ------------------------------------------------------------ scoring  */
 class Cdna4Tl final : public Tl {
   public:
@@ -2653,6 +2975,16 @@ class Cdna4Tl final : public Tl {
                     "min total message bytes for the SDMA alltoall "
                     "(measured crossover vs the gather kernel, "
                     "profiles/rocprof_kernels_r02.md)");
+        cfg.declare("TL_CDNA4", "P2P", "1",
+                    "device active-set bcast (p2p send/recv) over the peer "
+                    "mappings; 0 = device active sets are not supported "
+                    "(must match on every rank)");
+        cfg.declare("TL_CDNA4", "P2P_DEPTH", "8",
+                    "p2p mailbox ring depth per ordered pair (power of "
+                    "two <= 64; must match on every rank)");
+        cfg.declare("TL_CDNA4", "P2P_BLOCKS", "0",
+                    "p2p pull kernel grid size (workgroups of 256; 0 = "
+                    "size-derived, profiles/p2p_active_set.md)");
         if (!cfg.get_bool("TL_CDNA4", "ENABLE", true) ||
             !mc::hip_available()) {
             return nullptr;
@@ -2695,6 +3027,16 @@ class Cdna4Tl final : public Tl {
         c.ce_alltoall_min =
             cfg.get_size("TL_CDNA4", "CE_ALLTOALL_MIN",
                          192 * 1024 * 1024);
+        c.p2p       = cfg.get_bool("TL_CDNA4", "P2P", true);
+        c.p2p_depth = p2p_clamp_depth(
+            (long)cfg.get_int("TL_CDNA4", "P2P_DEPTH", 8));
+        c.p2p_blocks = (int)cfg.get_int("TL_CDNA4", "P2P_BLOCKS", 0);
+        if (c.p2p_blocks < 0) {
+            c.p2p_blocks = 0;
+        }
+        if (c.p2p_blocks > ec_hip::kP2pMaxBlocks) {
+            c.p2p_blocks = ec_hip::kP2pMaxBlocks;
+        }
         return new Cdna4TlTeam(tlc, team, c);
     }
 };
@@ -2717,6 +3059,9 @@ void Cdna4TlTeam::get_scores(Team *team, ScoreMap &map)
         r.alg_name = "gated_pipeline";
         r.init     = [self](const ucc_coll_args_t &args, Team *t,
                         Task **task) -> ucc_status_t {
+            if (args.mask & UCC_COLL_ARGS_FIELD_ACTIVE_SET) {
+                return UCC_ERR_NOT_SUPPORTED; /* active_set_p2p only */
+            }
             if (args.coll_type == UCC_COLL_TYPE_ALLREDUCE ||
                 args.coll_type == UCC_COLL_TYPE_REDUCE_SCATTER ||
                 args.coll_type == UCC_COLL_TYPE_REDUCE_SCATTERV) {
@@ -2755,6 +3100,11 @@ void Cdna4TlTeam::get_scores(Team *team, ScoreMap &map)
         r.alg_name = alg;
         r.init     = [self, fused](const ucc_coll_args_t &args, Team *t,
                                Task **task) -> ucc_status_t {
+            /* subset colls never take the team-wide slot sequence:
+             * non-members post nothing (active_set_p2p serves bcast) */
+            if (args.mask & UCC_COLL_ARGS_FIELD_ACTIVE_SET) {
+                return UCC_ERR_NOT_SUPPORTED;
+            }
             /* reductions need a supported dtype x op on device */
             if (args.coll_type == UCC_COLL_TYPE_ALLREDUCE ||
                 args.coll_type == UCC_COLL_TYPE_REDUCE ||
@@ -2796,6 +3146,32 @@ void Cdna4TlTeam::get_scores(Team *team, ScoreMap &map)
             map.add(ct, mt, r);
         }
     };
+    if (cfg_.p2p) {
+        ScoreRange r;
+        r.start    = 0;
+        r.end      = SIZE_MAX;
+        r.score    = 95;
+        r.tl_name  = "cdna4";
+        r.alg_name = "active_set_p2p";
+        r.init     = [self](const ucc_coll_args_t &args, Team *t,
+                        Task **task) -> ucc_status_t {
+            if (!(args.mask & UCC_COLL_ARGS_FIELD_ACTIVE_SET)) {
+                return UCC_ERR_NOT_SUPPORTED;
+            }
+            /* packed (non-contiguous generic) datatypes need a host
+             * pack/unpack pass: not on this path */
+            const ucc_datatype_t dt = args.src.info.datatype;
+            if (!ucc_dt_is_predefined(dt)) {
+                const ucc_generic_dt_ops_t *g = ucc_dt_generic_ops(dt);
+                if (!g || !(g->flags & UCC_GENERIC_DT_OPS_FLAG_CONTIG)) {
+                    return UCC_ERR_NOT_SUPPORTED;
+                }
+            }
+            *task = new ActiveSetBcastTask(t->ctx, self, args);
+            return UCC_OK;
+        };
+        map.add(UCC_COLL_TYPE_BCAST, UCC_MEMORY_TYPE_CUDA, r);
+    }
     add(UCC_COLL_TYPE_ALLREDUCE, 0, cfg_.fused_max, 100, "fused", true);
     if (Config::instance().get_bool("TL_CDNA4", "GATED", true)) {
         add_gated(UCC_COLL_TYPE_ALLREDUCE, cfg_.fused_max + 1, SIZE_MAX,

@@ -495,6 +495,11 @@ void RcclTlTeam::get_scores(Team *team, ScoreMap &map)
         r.alg_name = "rccl";
         r.init     = [self](const ucc_coll_args_t &args, Team *t,
                         Task **task) -> ucc_status_t {
+            /* a communicator-wide RCCL call cannot serve a rank subset:
+             * non-members post nothing */
+            if (args.mask & UCC_COLL_ARGS_FIELD_ACTIVE_SET) {
+                return UCC_ERR_NOT_SUPPORTED;
+            }
             *task = new RcclTask(t->ctx, self, args);
             return UCC_OK;
         };
