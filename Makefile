@@ -96,7 +96,19 @@ clean:
 check: all
 	python3 -m pytest tests/ -x -q -m "not gpu"
 
-.PHONY: all clean check
+# Compiled resource usage of the fused zero-copy allreduce: no scratch,
+# flagship at 3 waves/SIMD, depth 4 at >= 2 (tools/check_zc_isa.py). A
+# device-only compile of the gated kernel unit; run it after any change to
+# zc_data_phase or a compiler update.
+check-isa:
+	@mkdir -p $(BUILD)
+	$(HIPCC) $(filter-out -MMD -MP,$(CXXFLAGS)) --cuda-device-only \
+	    -Rpass-analysis=kernel-resource-usage \
+	    -c src/ec/kernels/ec_gated.hip -o $(BUILD)/ec_gated_isa.o \
+	    2> $(BUILD)/ec_gated_isa.txt
+	$(PYTHON) tools/check_zc_isa.py $(BUILD)/ec_gated_isa.txt
+
+.PHONY: all clean check check-isa
 
 # auto-generated header dependencies (-MMD)
 -include $(LIB_OBJS:.o=.d) $(BIND_OBJ:.o=.d)

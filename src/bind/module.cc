@@ -618,6 +618,92 @@ PYBIND11_MODULE(_core, m)
         },
         py::arg("dst"), py::arg("src"), py::arg("nbytes"),
         py::arg("blocks") = 0);
+    /* data-phase probe and kernel unit-test hook: `reps` back-to-back
+     * k_zc_data launches on one stream between two events, in-process;
+     * returns the milliseconds per launch. srcs are the ranks' buffer
+     * bases (the kernel adds sl_b), dsts are already offset by the slice
+     * start, as in the real path: n of them with zc_write, else the one
+     * my_out. Pointers may be IPC mappings (mem_map_import). */
+    m.def(
+        "ec_zc_data",
+        [](std::vector<uintptr_t> srcs, std::vector<uintptr_t> dsts,
+           uint64_t sl_b, uint64_t sl_e, int dt, int op, int zc_write,
+           double alpha, int blocks, int threads, int reps) {
+            const size_t n = srcs.size();
+            if (n < 2 || n > (size_t)ucc::ec_hip::kMaxRanks ||
+                dsts.size() != (zc_write ? n : (size_t)1) || sl_e < sl_b ||
+                blocks < 1 || blocks > ucc::ec_hip::kGatedMaxBlocks ||
+                reps < 1) {
+                throw std::runtime_error("ec_zc_data: bad arguments");
+            }
+            /* the kernel moves 16-byte packs */
+            bool aligned = sl_b % 16 == 0;
+            for (uintptr_t q : srcs) {
+                aligned = aligned && q != 0 && q % 16 == 0;
+            }
+            for (uintptr_t q : dsts) {
+                aligned = aligned && q != 0 && q % 16 == 0;
+            }
+            if (!aligned) {
+                throw std::runtime_error(
+                    "ec_zc_data: pointers and sl_b must be 16-byte aligned");
+            }
+            ucc::ec_hip::GatedArgs a{};
+            for (size_t r = 0; r < n; r++) {
+                a.peer_in[r] = (const void *)srcs[r];
+                if (zc_write) {
+                    a.peer_out[r] = (const void *)dsts[r];
+                }
+            }
+            a.my_out   = zc_write ? nullptr : (void *)dsts[0];
+            a.sl_b     = sl_b;
+            a.sl_e     = sl_e;
+            a.nranks   = (int)n;
+            a.dt       = (ucc_datatype_t)dt;
+            a.op       = (ucc_reduction_op_t)op;
+            a.alpha    = alpha;
+            a.zc_write = zc_write ? 1 : 0;
+            a.nblocks  = blocks;
+            hipStream_t st = nullptr;
+            hipEvent_t  e0 = nullptr, e1 = nullptr;
+            if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) !=
+                    hipSuccess ||
+                hipEventCreate(&e0) != hipSuccess ||
+                hipEventCreate(&e1) != hipSuccess) {
+                if (e0) {
+                    (void)hipEventDestroy(e0);
+                }
+                if (st) {
+                    (void)hipStreamDestroy(st);
+                }
+                throw std::runtime_error("ec_zc_data: no stream/events");
+            }
+            ucc_status_t rc = UCC_OK;
+            float        ms = 0.f;
+            (void)hipDeviceSynchronize();
+            (void)hipEventRecord(e0, st);
+            for (int i = 0; i < reps && rc == UCC_OK; i++) {
+                rc = ucc::ec_hip::zc_data(a, st, threads);
+            }
+            (void)hipEventRecord(e1, st);
+            const hipError_t he = hipStreamSynchronize(st);
+            if (he == hipSuccess) {
+                (void)hipEventElapsedTime(&ms, e0, e1);
+            }
+            (void)hipEventDestroy(e0);
+            (void)hipEventDestroy(e1);
+            (void)hipStreamDestroy(st);
+            check(rc, "zc_data");
+            if (he != hipSuccess) {
+                throw std::runtime_error(std::string("ec_zc_data: ") +
+                                         hipGetErrorString(he));
+            }
+            return (double)ms / reps;
+        },
+        py::arg("srcs"), py::arg("dsts"), py::arg("sl_b"), py::arg("sl_e"),
+        py::arg("dt"), py::arg("op"), py::arg("zc_write"),
+        py::arg("alpha"), py::arg("blocks"), py::arg("threads") = 256,
+        py::arg("reps") = 1);
     m.def("hip_device_count",
           []() { return ucc_amd_hip_device_count_c(); });
     /* raw (non-cache-hit) allocations done by the mc scratch mpool —

@@ -244,6 +244,20 @@ ucc_status_t staged_gather(const GatedArgs &a, hipStream_t s);
  * +nblocks, and for allreduce phase 2 +1 — those of the launches it
  * replaces. */
 ucc_status_t zc_allreduce(const GatedArgs &a, hipStream_t s);
+/* The data phase of zc_allreduce alone (k_zc_data): same device code and
+ * the same depth selection, but no flag is read or written, so it needs
+ * no peer and no team. Reads peer_in[0..nranks) + sl_b, writes
+ * peer_out[0..nranks) (zc_write = 1) or my_out (zc_write = 0); uses
+ * sl_b, sl_e, nranks, dt, op, alpha and nblocks and nothing else of `a`.
+ * threads: 64, 128 or 256 per block, 0 = what zc_allreduce would use.
+ * Measurement probe and kernel unit-test hook. */
+ucc_status_t zc_data(const GatedArgs &a, hipStream_t s, int threads = 0);
+/* The batching depth U (4, 2 or 1) that zc_allreduce and zc_data run at
+ * for this rank count, UCC_EC_REDUCE_DEPTH included. The host needs it
+ * to size the grid: how many blocks of k_zc_allreduce a CU holds depends
+ * on U (every U = 4 instantiation compiles to at least 2 waves/SIMD,
+ * some U = 2 ones to 1). */
+int zc_depth(int nranks);
 /* copy-engine gating (SDMA data path): pure wait on gw_phase/t_gather_wait
  * (1 block), and signal-phase-2-then-wait-team (full gated grid). */
 ucc_status_t gated_wait_only(const GatedArgs &a, hipStream_t s);

@@ -442,8 +442,8 @@ zc_batch_load(P (&x)[U][NR], const GatedArgs &a, int n, uint64_t i,
  * the arithmetic of k_staged_reduce's batched loop, element for element */
 template <typename T, int OP, int VEC, int U, int NR, typename P>
 __device__ __forceinline__ void
-zc_batch_reduce_store(const P (&x)[U][NR], const GatedArgs &a, int n,
-                      uint64_t i, uint64_t str)
+zc_batch_reduce_store(const P (&x)[U][NR], const GatedArgs &a, P *out,
+                      int n, uint64_t i, uint64_t str)
 {
     using A = typename Cvt<T>::A;
     A r[U][VEC];
@@ -476,45 +476,40 @@ zc_batch_reduce_store(const P (&x)[U][NR], const GatedArgs &a, int n,
             }
         }
     } else {
+        /* `out` is a.my_out read ahead of the zc_write branch (see
+         * zc_data_phase). At NR == 2 the in-branch read is kept: there
+         * the struct stays out of scratch either way, and the early read
+         * costs the flagship instantiation a waves/SIMD band (188
+         * instead of 159 VGPRs), as does reading it once above this
+         * loop. */
 #pragma unroll
         for (int u = 0; u < U; u++) {
-            ((P *)a.my_out)[i + (uint64_t)u * str] = o[u];
+            (NR > 2 ? out : (P *)a.my_out)[i + (uint64_t)u * str] = o[u];
         }
     }
 }
 
-/* One launch per zero-copy post (host-target mode only): the stage
- * signal, the reduce and the completion wait of the three-kernel pattern
- * in one grid of a.nblocks blocks. Counter effects are those of the
- * three launches (phase 0 +1, phase 1 +B, phase 2 +1), so every other
- * gated collective composes with it on the shared (slot,parity)
- * counters. zc_write = 1: allreduce, my reduced slice goes into every
- * rank's dst. zc_write = 0: reduce_scatter, my slice goes to my_out only
- * and phase 2 is neither waited on nor signalled. See
- * docs/GATED_PIPELINE.md "Fused zero-copy allreduce". */
+/* The data phase of the fused kernel — everything between its entry wait
+ * and its exit signal: the pipelined batches, their epilogue, the
+ * per-pack loop and the scalar tail over my slice [sl_b, sl_e) of every
+ * rank's src. No flag is read or written here, so k_zc_data below can
+ * time it without a peer process (docs/GATED_PIPELINE.md "Data phase
+ * and its probe"). */
 template <typename T, int OP, int VEC, int U>
-__global__ void __launch_bounds__(256) k_zc_allreduce(const GatedArgs a)
+__device__ __forceinline__ void zc_data_phase(const GatedArgs &a)
 {
     using A          = typename Cvt<T>::A;
     using P          = Pack<T, OP, VEC>;
     constexpr int NR = ZcPeers<U>::value;
-    /* entry: block 0 is this rank's stage launch — area-reuse waits
-     * (already satisfied in steady state), then "my stream reached this
-     * post" on phase 0 (+1, so this one increment is the last arriver
-     * and pushes the mirrors) */
-    if (blockIdx.x == 0) {
-        if (!zc_wait2(a, 1, a.t_sw_reduce, 2, a.t_sw_gather)) {
-            return;
-        }
-        gated_signal(a, 0, a.t_sig_stage, /*pub_done=*/false);
-    }
-    if (!zc_wait2(a, 0, a.t_stage, 2, a.t_prev_gather)) {
-        return;
-    }
     const uint64_t cnt = (a.sl_e - a.sl_b) / sizeof(T);
     const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t str = (uint64_t)gridDim.x * blockDim.x;
     const uint64_t nv  = cnt / VEC;
+    /* read before any zc_write branch: a load of my_out on one side and
+     * of peer_out[s] on the other would be merged into one load through
+     * a pointer INTO the argument struct, and that keeps the whole
+     * struct in scratch memory (observed in gfx950 ISA, U = 2) */
+    P *const out = (P *)a.my_out;
     /* 2 <= nranks <= NR (launcher-checked). At NR == 2 that pins n, so
      * the uniform peer guards fold away. This is what lets the pipeline
      * work: behind a branch that may or may not have issued loads the
@@ -542,24 +537,24 @@ __global__ void __launch_bounds__(256) k_zc_allreduce(const GatedArgs a)
             zc_batch_load<P, U, NR>(xa, a, n, i, str);
             while (i + 2 * bs + tail < nv) {
                 zc_batch_load<P, U, NR>(xb, a, n, i + bs, str);
-                zc_batch_reduce_store<T, OP, VEC, U, NR, P>(xa, a, n, i,
-                                                            str);
+                zc_batch_reduce_store<T, OP, VEC, U, NR, P>(xa, a, out, n,
+                                                            i, str);
                 zc_batch_load<P, U, NR>(xa, a, n, i + 2 * bs, str);
-                zc_batch_reduce_store<T, OP, VEC, U, NR, P>(xb, a, n,
+                zc_batch_reduce_store<T, OP, VEC, U, NR, P>(xb, a, out, n,
                                                             i + bs, str);
                 i += 2 * bs;
             }
             /* epilogue: one or two full batches left */
             if (i + bs + tail < nv) {
                 zc_batch_load<P, U, NR>(xb, a, n, i + bs, str);
-                zc_batch_reduce_store<T, OP, VEC, U, NR, P>(xa, a, n, i,
-                                                            str);
-                zc_batch_reduce_store<T, OP, VEC, U, NR, P>(xb, a, n,
+                zc_batch_reduce_store<T, OP, VEC, U, NR, P>(xa, a, out, n,
+                                                            i, str);
+                zc_batch_reduce_store<T, OP, VEC, U, NR, P>(xb, a, out, n,
                                                             i + bs, str);
                 i += 2 * bs;
             } else {
-                zc_batch_reduce_store<T, OP, VEC, U, NR, P>(xa, a, n, i,
-                                                            str);
+                zc_batch_reduce_store<T, OP, VEC, U, NR, P>(xa, a, out, n,
+                                                            i, str);
                 i += bs;
             }
         }
@@ -589,7 +584,7 @@ __global__ void __launch_bounds__(256) k_zc_allreduce(const GatedArgs a)
                 }
             }
         } else {
-            ((P *)a.my_out)[i] = o;
+            out[i] = o;
         }
     }
     for (uint64_t t = nv * VEC + tid; t < cnt; t += str) {
@@ -613,9 +608,37 @@ __global__ void __launch_bounds__(256) k_zc_allreduce(const GatedArgs a)
                 }
             }
         } else {
-            ((T *)a.my_out)[t] = ov;
+            ((T *)out)[t] = ov;
         }
     }
+}
+
+/* One launch per zero-copy post (host-target mode only): the stage
+ * signal, the reduce and the completion wait of the three-kernel pattern
+ * in one grid of a.nblocks blocks. Counter effects are those of the
+ * three launches (phase 0 +1, phase 1 +B, phase 2 +1), so every other
+ * gated collective composes with it on the shared (slot,parity)
+ * counters. zc_write = 1: allreduce, my reduced slice goes into every
+ * rank's dst. zc_write = 0: reduce_scatter, my slice goes to my_out only
+ * and phase 2 is neither waited on nor signalled. See
+ * docs/GATED_PIPELINE.md "Fused zero-copy allreduce". */
+template <typename T, int OP, int VEC, int U>
+__global__ void __launch_bounds__(256) k_zc_allreduce(const GatedArgs a)
+{
+    /* entry: block 0 is this rank's stage launch — area-reuse waits
+     * (already satisfied in steady state), then "my stream reached this
+     * post" on phase 0 (+1, so this one increment is the last arriver
+     * and pushes the mirrors) */
+    if (blockIdx.x == 0) {
+        if (!zc_wait2(a, 1, a.t_sw_reduce, 2, a.t_sw_gather)) {
+            return;
+        }
+        gated_signal(a, 0, a.t_sig_stage, /*pub_done=*/false);
+    }
+    if (!zc_wait2(a, 0, a.t_stage, 2, a.t_prev_gather)) {
+        return;
+    }
+    zc_data_phase<T, OP, VEC, U>(a);
     /* exit: every block counts on phase 1; the last arriver pushed the
      * mirrors and stays on as this rank's gather launch: wait for the
      * TEAM's reduces (every peer has written my dst and stopped reading
@@ -632,6 +655,15 @@ __global__ void __launch_bounds__(256) k_zc_allreduce(const GatedArgs a)
         __hip_atomic_store(a.done_host, a.done_seq, __ATOMIC_RELEASE,
                            __HIP_MEMORY_SCOPE_SYSTEM);
     }
+}
+
+/* The data phase alone, for measurement and unit tests: no flags, no
+ * waits, no signals, so it runs without a peer process and hardware
+ * counters can be collected on it. */
+template <typename T, int OP, int VEC, int U>
+__global__ void __launch_bounds__(256) k_zc_data(const GatedArgs a)
+{
+    zc_data_phase<T, OP, VEC, U>(a);
 }
 
 /* ----------------------------------------------------------- launchers */
@@ -738,22 +770,46 @@ ucc_status_t staged_reduce(const GatedArgs &a, hipStream_t s)
                                         a.op, a, s);
 }
 
+/* Batching depth of the zero-copy data phase. It unrolls kMaxRanks / U
+ * peers, so the depth is halved until U * nranks fits; depth 8 runs as 4
+ * (the second pack buffer already doubles the bytes in flight). */
+int zc_depth(int nranks)
+{
+    int depth = std::min(reduce_depth(nranks), 4);
+    while (depth > 1 && depth * nranks > kMaxRanks) {
+        depth /= 2;
+    }
+    return depth;
+}
+
+/* threads per block of the zero-copy kernels, compiled for at most 256 */
+static int zc_threads()
+{
+    return reduce_knobs().threads == 128 ? 128 : 256;
+}
+
 template <typename T, int OP> struct LaunchZcAllreduce {
     static ucc_status_t run(const GatedArgs &a, hipStream_t s)
     {
-        /* The kernel unrolls kMaxRanks / U peers, so the depth is halved
-         * until U * nranks fits; depth 8 runs as 4 (the second pack
-         * buffer already doubles the bytes in flight). The kernel is
-         * compiled for blocks of at most 256 threads. */
-        int depth = std::min(reduce_depth(a.nranks), 4);
-        while (depth > 1 && depth * a.nranks > kMaxRanks) {
-            depth /= 2;
-        }
-        const int threads = reduce_knobs().threads == 128 ? 128 : 256;
-        return launch_by_depth<4>(depth, [&](auto u) {
+        return launch_by_depth<4>(zc_depth(a.nranks), [&](auto u) {
             hipLaunchKernelGGL(
                 (k_zc_allreduce<T, OP, VecOf<T>::value, decltype(u)::value>),
-                dim3(gated_grid(a)), dim3(threads), 0, s, a);
+                dim3(gated_grid(a)), dim3(zc_threads()), 0, s, a);
+        });
+    }
+};
+
+struct ZcDataLaunch {
+    const GatedArgs &a;
+    int              threads;
+};
+template <typename T, int OP> struct LaunchZcData {
+    static ucc_status_t run(const ZcDataLaunch &l, hipStream_t s)
+    {
+        return launch_by_depth<4>(zc_depth(l.a.nranks), [&](auto u) {
+            hipLaunchKernelGGL(
+                (k_zc_data<T, OP, VecOf<T>::value, decltype(u)::value>),
+                dim3(gated_grid(l.a)), dim3(l.threads), 0, s, l.a);
         });
     }
 };
@@ -765,6 +821,18 @@ ucc_status_t zc_allreduce(const GatedArgs &a, hipStream_t s)
     }
     return dispatch<LaunchZcAllreduce>(fold_complex(a.dt, a.op, nullptr),
                                        a.op, a, s);
+}
+
+ucc_status_t zc_data(const GatedArgs &a, hipStream_t s, int threads)
+{
+    if (a.nranks < 2 || a.nranks > kMaxRanks || a.sl_e < a.sl_b ||
+        (threads != 0 && threads != 64 && threads != 128 &&
+         threads != 256)) {
+        return UCC_ERR_INVALID_PARAM;
+    }
+    const ZcDataLaunch l{a, threads ? threads : zc_threads()};
+    return dispatch<LaunchZcData>(fold_complex(a.dt, a.op, nullptr), a.op,
+                                  l, s);
 }
 
 } // namespace ec_hip

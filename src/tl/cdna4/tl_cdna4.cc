@@ -2221,20 +2221,6 @@ class GatedCollTask final : public Cdna4Task {
             nfrags_ = 1;
         }
         auto &L          = tt_->gated_launch_;
-        /* grid size: measured crossover on the 2-proc rig
-         * (profiles/rocprof_kernels_r02.md): 64 blocks win below
-         * ~160 MiB, 96 above (single-frag zc reduce fills more CUs on
-         * big slices). The launch ledger accumulates BLOCK counts, so
-         * per-collective grids compose on shared (slot,parity)
-         * counters. */
-        const int nblk =
-            tt_->cfg_.gated_blocks
-                ? tt_->cfg_.gated_blocks
-                : (nfrags_ == 1 && total_ >= 160u * 1024 * 1024
-                       ? 128 /* re-measured after 1-block gates:
-                                profiles/rocprof_kernels_r02.md */
-                       : ec_hip::kGatedBlocks);
-        const uint64_t B = (uint64_t)nblk;
         /* zero-copy allreduce / reduce_scatter posted from the host:
          * the stage signal, the reduce and the completion wait run as
          * ONE kernel (docs/GATED_PIPELINE.md "Fused zero-copy
@@ -2245,6 +2231,36 @@ class GatedCollTask final : public Cdna4Task {
             (ct_ == UCC_COLL_TYPE_ALLREDUCE ||
              ct_ == UCC_COLL_TYPE_REDUCE_SCATTER) &&
             Config::instance().get_bool("TL_CDNA4", "ZC_FUSED", true);
+        /* grid size, measured on the 2-proc rig. 64 blocks by default.
+         * One-kernel allreduce of 2 ranks at depth 4, the one case
+         * measured (profiles/zc_data_phase.md): 192 blocks from 128 MiB
+         * up; every 256 MiB run at 192 beat every run at 128.
+         * Residency: all blocks of a rank spin at entry until every
+         * peer's block 0 has run, so the ranks' grids must fit the card
+         * together. Every U = 4 instantiation of k_zc_allreduce
+         * compiles to at least 2 waves/SIMD (VGPRs + AGPRs), i.e. 2
+         * blocks of 256 threads per CU, 512 per card, and 192 is below
+         * half of that. It does NOT hold at U = 2: the int8/uint8
+         * instantiations there take 256 VGPRs plus AGPRs, 1 block per
+         * CU, 256 per card, so 3 or 4 ranks of 192 blocks on one card
+         * could not all be placed. Hence the conditions on n_ and on
+         * the depth the launcher will pick (UCC_EC_REDUCE_DEPTH, like
+         * GATED_BLOCKS, has to agree on all ranks: B enters the
+         * ledger). Everything else keeps the earlier rule
+         * (profiles/rocprof_kernels_r02.md): 128 from 160 MiB up for a
+         * single fragment. The launch ledger accumulates BLOCK counts,
+         * so per-collective grids compose on shared (slot,parity)
+         * counters. */
+        const size_t MiB    = 1024 * 1024;
+        const bool   big_ar = zc_fused && ct_ == UCC_COLL_TYPE_ALLREDUCE &&
+                            n_ == 2 && ec_hip::zc_depth(2) == 4 &&
+                            total_ >= 128 * MiB;
+        const int nblk =
+            tt_->cfg_.gated_blocks                  ? tt_->cfg_.gated_blocks
+            : big_ar                                ? 192
+            : nfrags_ == 1 && total_ >= 160 * MiB   ? 128
+                                                    : ec_hip::kGatedBlocks;
+        const uint64_t B = (uint64_t)nblk;
         for (size_t f = 0; f < nfrags_; f++) {
             const uint32_t p   = (uint32_t)(f & 1);
             const size_t   off = f * gran_;

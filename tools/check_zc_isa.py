@@ -1,0 +1,79 @@
+#!/usr/bin/env python3
+"""Check the compiled resource usage of the fused zero-copy allreduce.
+
+Reads the -Rpass-analysis=kernel-resource-usage remarks of
+src/ec/kernels/ec_gated.hip (file argument or stdin; `make check-isa`
+produces them) and fails unless
+
+ 1. no k_zc_allreduce instantiation uses scratch memory (the kernel
+    argument struct and the pack buffers stay in registers:
+    docs/GATED_PIPELINE.md "Data phase and its probe");
+ 2. the flagship k_zc_allreduce<bf16,SUM,8,4> keeps 3 waves/SIMD;
+ 3. every depth-4 instantiation keeps at least 2 waves/SIMD, i.e. 2
+    blocks of 256 threads per CU: the residency arithmetic behind the
+    192-block grid in src/tl/cdna4/tl_cdna4.cc.
+
+Occupancy is the compiler's figure, VGPRs and AGPRs together."""
+
+import re
+import sys
+
+NAME = re.compile(r"k_zc_allreduceI(.+?)Li(\d+)ELi(\d+)ELi(\d+)EEEv")
+FLAGSHIP = ("NS0_6bf16_tE", 0, 8, 4)
+
+
+def parse(text):
+    out = {}
+    for blk in re.split(r"(?=remark: [^\n]*Function Name: )", text):
+        m = re.search(r"Function Name: (\S+)", blk)
+        n = NAME.search(m.group(1)) if m else None
+        if not n:
+            continue
+
+        def field(key):
+            return int(re.search(key + r": (\d+)", blk).group(1))
+
+        key = (n.group(1), int(n.group(2)), int(n.group(3)),
+               int(n.group(4)))
+        out[key] = dict(vgprs=field("VGPRs"), agprs=field("AGPRs"),
+                        scratch=field(r"ScratchSize \[bytes/lane\]"),
+                        waves=field(r"Occupancy \[waves/SIMD\]"))
+    return out
+
+
+def check(kernels):
+    bad = []
+    if FLAGSHIP not in kernels:
+        return ["flagship k_zc_allreduce<bf16,0,8,4> not found "
+                f"({len(kernels)} instantiations parsed)"]
+    for key, k in sorted(kernels.items()):
+        if k["scratch"]:
+            bad.append(f"{key}: {k['scratch']} B/lane of scratch")
+        if key[3] == 4 and k["waves"] < 2:
+            bad.append(f"{key}: {k['waves']} waves/SIMD at depth 4 "
+                       f"({k['vgprs']} VGPRs + {k['agprs']} AGPRs)")
+    f = kernels[FLAGSHIP]
+    if f["waves"] < 3:
+        bad.append(f"flagship: {f['waves']} waves/SIMD "
+                   f"({f['vgprs']} VGPRs + {f['agprs']} AGPRs), want 3")
+    return bad
+
+
+def main():
+    text = open(sys.argv[1]).read() if len(sys.argv) > 1 else sys.stdin.read()
+    kernels = parse(text)
+    bad = check(kernels)
+    for b in bad:
+        print("check_zc_isa:", b)
+    if bad:
+        return 1
+    f = kernels[FLAGSHIP]
+    low = min(k["waves"] for key, k in kernels.items() if key[3] == 4)
+    print(f"check_zc_isa ok: {len(kernels)} k_zc_allreduce instantiations, "
+          f"no scratch; flagship {f['vgprs']} VGPRs, {f['waves']} "
+          f"waves/SIMD; depth 4 at least {low} waves/SIMD")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
