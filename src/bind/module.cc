@@ -15,6 +15,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <tuple>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -704,6 +705,52 @@ PYBIND11_MODULE(_core, m)
         py::arg("dt"), py::arg("op"), py::arg("zc_write"),
         py::arg("alpha"), py::arg("blocks"), py::arg("threads") = 256,
         py::arg("reps") = 1);
+    /* kernel unit-test hook: one ring_step launch on the null stream,
+     * in-process, synchronised. pieces: up to kMaxRings tuples
+     * (in, local, out, dst, count), 0 = null pointer. Returns the status
+     * instead of throwing on UCC_ERR_NOT_SUPPORTED so that tests can see a
+     * refused dtype x op. */
+    m.def(
+        "ec_ring_step",
+        [](std::vector<std::tuple<uintptr_t, uintptr_t, uintptr_t, uintptr_t,
+                                  uint64_t>> pieces,
+           int dt, int op, double alpha, int in_acc, int out_acc,
+           int blocks) {
+            if (pieces.empty() ||
+                pieces.size() > (size_t)ucc::ec_hip::kMaxRings) {
+                throw std::runtime_error("ec_ring_step: 1..4 pieces");
+            }
+            ucc::ec_hip::RingStepArgs a{};
+            a.n_rings = (int)pieces.size();
+            for (size_t k = 0; k < pieces.size(); k++) {
+                a.piece[k].in    = (const void *)std::get<0>(pieces[k]);
+                a.piece[k].local = (const void *)std::get<1>(pieces[k]);
+                a.piece[k].out   = (void *)std::get<2>(pieces[k]);
+                a.piece[k].dst   = (void *)std::get<3>(pieces[k]);
+                a.piece[k].count = std::get<4>(pieces[k]);
+            }
+            a.dt      = (ucc_datatype_t)dt;
+            a.op      = (ucc_reduction_op_t)op;
+            a.alpha   = alpha;
+            a.in_acc  = in_acc;
+            a.out_acc = out_acc;
+            a.nblocks = blocks;
+            ucc_status_t st = ucc::ec_hip::ring_step(a, nullptr);
+            if (st == UCC_ERR_NOT_SUPPORTED) {
+                return (int)st;
+            }
+            check(st, "ring_step");
+            const hipError_t he = hipDeviceSynchronize();
+            if (he != hipSuccess) {
+                throw std::runtime_error(std::string("ec_ring_step: ") +
+                                         hipGetErrorString(he));
+            }
+            return (int)UCC_OK;
+        },
+        py::arg("pieces"), py::arg("dt"), py::arg("op"), py::arg("alpha"),
+        py::arg("in_acc"), py::arg("out_acc"), py::arg("blocks") = 0);
+    m.def("ec_ring_step_launches",
+          []() { return ucc::ec_hip::ring_step_launches(); });
     m.def("hip_device_count",
           []() { return ucc_amd_hip_device_count_c(); });
     /* raw (non-cache-hit) allocations done by the mc scratch mpool —

@@ -296,6 +296,57 @@ struct P2pPullArgs {
 int          p2p_auto_blocks(uint64_t len);
 ucc_status_t p2p_pull(const P2pPullArgs &a, hipStream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Ring step (host-gated multi-ring reduce_scatter / allgather / allreduce,
+ * src/tl/cdna4/ring_plan.h): ONE launch serves every ring of one step, its
+ * workgroups dealt over the pieces by size. The kernel never waits, reads
+ * no flag and does no atomic; the host gates the launch and completion is
+ * the stream event.
+ *
+ * Per element of a piece, T the datatype and A its accumulator type
+ * (Cvt<T>::A: f32 for the 8/16-bit floats, else T):
+ *   acc = op(in, local) when both are given, else the one that is given;
+ *         `in` is read as A when in_acc, else as T and widened; `local` is
+ *         always T.
+ *   dst gets T: alpha * acc converted once (docs/USER_GUIDE.md, "Reduction
+ *         numerics").
+ *   out gets the raw accumulator (no alpha, no rounding) when out_acc, else
+ *         exactly the bits dst gets.
+ * The travelling partial stays in A so that the ring rounds once, at the
+ * final store, like every other reduction here — not once per hop.
+ *
+ * With local == nullptr in every piece and in_acc = out_acc = 0 the step is
+ * a byte copy (one load, up to two stores per pack); dt only gives the
+ * element size and op is ignored.
+ *
+ * Any count is legal, 0 included; null `out` / `dst` are skipped. A piece
+ * whose non-null pointers are all 16-byte aligned moves 16-byte packs of T,
+ * any other goes element by element. No access falls outside
+ * [ptr, ptr + count) of any buffer. dtype x op as in reduce(); op 12 is SUM
+ * with alpha. */
+constexpr int kMaxRings = 4;
+struct RingPiece {
+    const void *in;
+    const void *local;
+    void       *out;
+    void       *dst;
+    uint64_t    count;
+};
+struct RingStepArgs {
+    RingPiece          piece[kMaxRings];
+    int                n_rings;
+    ucc_datatype_t     dt;
+    ucc_reduction_op_t op;
+    double             alpha;
+    int                in_acc, out_acc;
+    int                nblocks; /* grid size; 0 = size-derived */
+};
+ucc_status_t ring_step(const RingStepArgs &a, hipStream_t s);
+/* ring_step() calls accepted so far (a step whose pieces are all empty
+ * launches nothing and still counts); the ring tests read it to prove that
+ * the ring ran and how many steps it took */
+uint64_t ring_step_launches();
+
 } // namespace ec_hip
 } // namespace ucc
 

@@ -35,6 +35,7 @@
 #include "../../mc/mc.h"
 #include "../shm/slot_seg.h"
 #include "p2p_mbox.h"
+#include "ring_plan.h"
 
 namespace ucc {
 namespace {
@@ -50,6 +51,9 @@ static inline void hip_warn_on_err(hipError_t e, const char *what)
 #define HIPWARN(expr) hip_warn_on_err((expr), #expr)
 
 using ec_hip::kMaxRanks;
+static_assert(kRingMaxRings == ec_hip::kMaxRings &&
+                  kRingMaxRanks == ec_hip::kMaxRanks,
+              "ring_plan.h and ec_hip.h disagree");
 
 /* v-coll count/displacement accessors honoring the 64-bit flags
  * (reference: ucc_coll_utils count conventions). */
@@ -98,6 +102,8 @@ struct Cdna4Cfg {
     bool     p2p;        /* device active-set bcast (p2p send/recv)      */
     uint32_t p2p_depth;  /* mailbox ring depth, power of two <= 64       */
     int      p2p_blocks; /* pull kernel grid size; 0 = size-derived      */
+    bool     ring;       /* offer the multi-ring algorithms              */
+    int      ring_nrings; /* rings to use, 0 = auto (ring_plan.h)        */
 };
 
 class Cdna4Tl;
@@ -2666,6 +2672,236 @@ class GatedCollTask final : public Cdna4Task {
     }
 };
 
+/* Host-gated multi-ring reduce_scatter / allgather / allreduce: the
+ * link-partitioned alternative to the direct (staged_linear,
+ * gated_pipeline) algorithms, opt-in through UCC_TL_CDNA4_RING. The
+ * schedule is ring_plan.h; this task resolves its offsets to pointers and
+ * drives it the way StagedTask drives its phases: one ec_hip::ring_step
+ * launch per step on comp(), each gated ON THE HOST on the shm step
+ * counters of the ring neighbours, hand-offs at kernel boundaries only. The
+ * kernel never waits, so the in-process jig runs it at any rank count and a
+ * dead peer ends as a request timeout.
+ *
+ * The outbox of parity p is area(me, slot, p, 0); the travelling partial
+ * stays in accumulator type (f32 for the 8/16-bit floats), which is why
+ * the fragment width is chunk / sizeof(acc). Launch g publishes g + 1 once
+ * its event has completed. Launch 0 waits for ALL ranks to have closed the
+ * slot's previous use, like every staged task: that use may have been a
+ * direct algorithm, whose readers are not only the ring neighbours. */
+class RingTask final : public Cdna4Task {
+  public:
+    using Cdna4Task::Cdna4Task;
+
+    /* what of `a` the plan needs; false: not a ring collective */
+    struct Shape {
+        RingColl       coll;
+        bool           inplace;
+        ucc_datatype_t dt;
+        uint64_t       count; /* per rank (rs, ag) or whole vector (ar) */
+        size_t         dtsz, accsz;
+        const uint8_t *sbuf;
+        uint8_t       *dbuf;
+    };
+    static bool shape_of(const ucc_coll_args_t &a, uint32_t me, uint32_t n,
+                         Shape *s)
+    {
+        s->inplace = a.flags & UCC_COLL_ARGS_FLAG_IN_PLACE;
+        s->dt      = a.dst.info.datatype;
+        if (!ucc_dt_is_predefined(s->dt)) {
+            return false;
+        }
+        s->dtsz = ucc_dt_size(s->dt);
+        uint8_t       *dst = (uint8_t *)a.dst.info.buffer;
+        const uint8_t *src = (const uint8_t *)a.src.info.buffer;
+        switch (a.coll_type) {
+        case UCC_COLL_TYPE_ALLREDUCE:
+            s->coll  = RING_ALLREDUCE;
+            s->count = a.dst.info.count;
+            s->dbuf  = dst;
+            s->sbuf  = s->inplace ? dst : src;
+            break;
+        case UCC_COLL_TYPE_REDUCE_SCATTER:
+            s->coll = RING_REDUCE_SCATTER;
+            if (s->inplace) {
+                s->count = a.dst.info.count / n;
+                s->sbuf  = dst;
+                s->dbuf  = dst + (size_t)me * s->count * s->dtsz;
+            } else {
+                s->count = a.dst.info.count;
+                s->sbuf  = src;
+                s->dbuf  = dst;
+            }
+            break;
+        case UCC_COLL_TYPE_ALLGATHER:
+            /* pure data movement: planned and copied as bytes */
+            s->coll  = RING_ALLGATHER;
+            s->count = a.dst.info.count * s->dtsz / n;
+            s->dt    = UCC_DT_UINT8;
+            s->dtsz  = 1;
+            s->dbuf  = dst;
+            s->sbuf  = s->inplace ? dst + (size_t)me * s->count : src;
+            break;
+        default: return false;
+        }
+        if (s->coll != RING_ALLGATHER) {
+            /* complex SUM / AVG: float on 2x the elements */
+            const bool c32 = s->dt == UCC_DT_FLOAT32_COMPLEX;
+            const bool c64 = s->dt == UCC_DT_FLOAT64_COMPLEX;
+            if ((c32 || c64) &&
+                (a.op == UCC_OP_SUM || a.op == UCC_OP_AVG)) {
+                s->dt = c32 ? UCC_DT_FLOAT32 : UCC_DT_FLOAT64;
+                s->count *= 2;
+                s->dtsz /= 2;
+            }
+        }
+        const bool narrow =
+            s->dt == UCC_DT_BFLOAT16 || s->dt == UCC_DT_FLOAT16 ||
+            s->dt == UCC_DT_FLOAT8_E4M3 || s->dt == UCC_DT_FLOAT8_E5M2;
+        s->accsz = narrow ? sizeof(float) : s->dtsz;
+        return true;
+    }
+
+    /* init-time check: everything post() relies on, so that a refusal
+     * happens before the request takes a place in the post order */
+    static bool supported(const ucc_coll_args_t &a, Cdna4TlTeam *tt)
+    {
+        Shape    s;
+        RingPlan p;
+        const uint32_t n = tt->team_->size;
+        if (!shape_of(a, tt->team_->rank, n, &s)) {
+            return false;
+        }
+        if (s.coll != RING_ALLGATHER && !ec_hip::op_supported(s.dt, a.op)) {
+            return false;
+        }
+        return ring_plan_init(&p, (int)n, (int)tt->team_->rank,
+                              tt->cfg_.ring_nrings, s.coll, s.inplace,
+                              s.count, s.dtsz, s.accsz, tt->cfg_.chunk) &&
+               ring_plan_launches(p) + 1 < kCap;
+    }
+
+    ucc_status_t post() override
+    {
+        begin_use();
+        if (!shape_of(a_, me_, n_, &s_) ||
+            !ring_plan_init(&plan_, (int)n_, (int)me_, tt_->cfg_.ring_nrings,
+                            s_.coll, s_.inplace, s_.count, s_.dtsz, s_.accsz,
+                            tt_->cfg_.chunk)) {
+            return UCC_ERR_NOT_SUPPORTED; /* supported() said otherwise */
+        }
+        op_    = a_.op;
+        alpha_ = 1.0;
+        if (op_ == UCC_OP_AVG) {
+            op_    = (ucc_reduction_op_t)12; /* SUM + alpha */
+            alpha_ = 1.0 / (double)n_;
+        }
+        n_nb_     = ring_plan_neighbours(plan_, nb_);
+        total_    = ring_plan_launches(plan_);
+        g_        = 0;
+        launched_ = false;
+        status    = UCC_INPROGRESS;
+        return progress();
+    }
+
+    ucc_status_t progress() override
+    {
+        while (g_ < total_) {
+            if (!launched_) {
+                if (!gate()) {
+                    return UCC_INPROGRESS;
+                }
+                ucc_status_t st = launch();
+                if (st != UCC_OK) {
+                    close_slot();
+                    return st;
+                }
+                HIPWARN(hipEventRecord(ev(0), comp()));
+                launched_ = true;
+            }
+            hipError_t e = hipEventQuery(ev(0));
+            if (e == hipErrorNotReady) {
+                return UCC_INPROGRESS;
+            }
+            if (e != hipSuccess) {
+                close_slot();
+                return UCC_ERR_NO_RESOURCE;
+            }
+            launched_ = false;
+            g_++;
+            publish(g_);
+        }
+        close_slot();
+        return UCC_OK;
+    }
+
+  private:
+    bool gate()
+    {
+        if (g_ == 0) {
+            return all_ge(0);
+        }
+        for (int i = 0; i < n_nb_; i++) {
+            if (tt_->seg_.step(slot_, (uint32_t)nb_[i])
+                    ->load(std::memory_order_acquire) < base_ + g_) {
+                return false;
+            }
+        }
+        return true;
+    }
+
+    ucc_status_t launch()
+    {
+        RingLaunch l;
+        ring_plan_launch(plan_, g_ / (uint64_t)plan_.L,
+                         (int)(g_ % (uint64_t)plan_.L), &l);
+        const size_t in_sz  = l.in_acc ? s_.accsz : s_.dtsz;
+        const size_t out_sz = l.out_acc ? s_.accsz : s_.dtsz;
+        ec_hip::RingStepArgs ra{};
+        ra.n_rings = l.npieces;
+        ra.dt      = s_.dt;
+        ra.op      = op_;
+        ra.alpha   = l.final_rs ? alpha_ : 1.0;
+        ra.in_acc  = l.in_acc;
+        ra.out_acc = l.out_acc;
+        ra.nblocks = 0;
+        uint8_t *outbox = tt_->area(me_, slot_, (uint32_t)l.out_parity, 0);
+        for (int k = 0; k < l.npieces; k++) {
+            const RingPieceDesc &d  = l.p[k];
+            ec_hip::RingPiece   &pc = ra.piece[k];
+            pc.count                = d.count;
+            if (d.count == 0) {
+                continue;
+            }
+            if (l.in_from_src) {
+                pc.in = s_.sbuf + d.src_off * s_.dtsz;
+            } else if (l.use_in) {
+                pc.in = tt_->area((uint32_t)d.left, slot_,
+                                  (uint32_t)l.in_parity, 0) +
+                        d.box_off * in_sz;
+            }
+            if (l.use_local) {
+                pc.local = s_.sbuf + d.src_off * s_.dtsz;
+            }
+            if (l.use_out) {
+                pc.out = outbox + d.box_off * out_sz;
+            }
+            if (l.use_dst) {
+                pc.dst = s_.dbuf + d.dst_off * s_.dtsz;
+            }
+        }
+        return ec_hip::ring_step(ra, comp());
+    }
+
+    Shape              s_{};
+    RingPlan           plan_;
+    ucc_reduction_op_t op_    = UCC_OP_SUM;
+    double             alpha_ = 1.0;
+    int                nb_[2 * kRingMaxRings] = {};
+    int                n_nb_     = 0;
+    uint64_t           total_    = 0, g_ = 0;
+    bool               launched_ = false;
+};
+
 /* Device active-set bcast: a transfer of one device buffer from `root` to
  * the other members of the strided rank subset {start, stride, size}. A
  * 2-member set with the sender as root is a send/recv (reference: tl/ucp
@@ -3001,6 +3237,15 @@ class Cdna4Tl final : public Tl {
         cfg.declare("TL_CDNA4", "P2P_BLOCKS", "0",
                     "p2p pull kernel grid size (workgroups of 256; 0 = "
                     "size-derived, profiles/p2p_active_set.md)");
+        cfg.declare("TL_CDNA4", "RING", "0",
+                    "offer the host-gated multi-ring (link-partitioned) "
+                    "allreduce / reduce_scatter / allgather as algorithm "
+                    "'ring' at score 70, below every direct algorithm: "
+                    "select it with UCC_TUNE (must match on every rank)");
+        cfg.declare("TL_CDNA4", "RING_NRINGS", "0",
+                    "rings of the 'ring' algorithm, one per stride coprime "
+                    "to the team size, at most 4 (0 = auto: "
+                    "min(4, phi(n)); must match on every rank)");
         if (!cfg.get_bool("TL_CDNA4", "ENABLE", true) ||
             !mc::hip_available()) {
             return nullptr;
@@ -3052,6 +3297,14 @@ class Cdna4Tl final : public Tl {
         }
         if (c.p2p_blocks > ec_hip::kP2pMaxBlocks) {
             c.p2p_blocks = ec_hip::kP2pMaxBlocks;
+        }
+        c.ring        = cfg.get_bool("TL_CDNA4", "RING", false);
+        c.ring_nrings = (int)cfg.get_int("TL_CDNA4", "RING_NRINGS", 0);
+        if (c.ring_nrings < 0) {
+            c.ring_nrings = 0;
+        }
+        if (c.ring_nrings > kRingMaxRings) {
+            c.ring_nrings = kRingMaxRings;
         }
         return new Cdna4TlTeam(tlc, team, c);
     }
@@ -3214,6 +3467,32 @@ void Cdna4TlTeam::get_scores(Team *team, ScoreMap &map)
     add(UCC_COLL_TYPE_GATHERV, 0, SIZE_MAX, 80, "staged_linear", false);
     add(UCC_COLL_TYPE_SCATTER, 0, SIZE_MAX, 80, "staged_linear", false);
     add(UCC_COLL_TYPE_SCATTERV, 0, SIZE_MAX, 80, "staged_linear", false);
+    if (cfg_.ring) {
+        /* opt-in, and even then below every direct algorithm until
+         * UCC_TUNE lifts it */
+        ScoreRange r;
+        r.start    = 0;
+        r.end      = SIZE_MAX;
+        r.score    = 70;
+        r.tl_name  = "cdna4";
+        r.alg_name = "ring";
+        r.init     = [self](const ucc_coll_args_t &args, Team *t,
+                        Task **task) -> ucc_status_t {
+            if ((args.mask & UCC_COLL_ARGS_FIELD_ACTIVE_SET) ||
+                !RingTask::supported(args, self)) {
+                return UCC_ERR_NOT_SUPPORTED;
+            }
+            *task = new RingTask(t->ctx, self, args);
+            return UCC_OK;
+        };
+        for (auto ct : {UCC_COLL_TYPE_ALLREDUCE, UCC_COLL_TYPE_REDUCE_SCATTER,
+                        UCC_COLL_TYPE_ALLGATHER}) {
+            for (auto mt :
+                 {UCC_MEMORY_TYPE_CUDA, UCC_MEMORY_TYPE_CUDA_MANAGED}) {
+                map.add(ct, mt, r);
+            }
+        }
+    }
 }
 
 } // namespace
