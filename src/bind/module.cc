@@ -705,6 +705,81 @@ PYBIND11_MODULE(_core, m)
         py::arg("dt"), py::arg("op"), py::arg("zc_write"),
         py::arg("alpha"), py::arg("blocks"), py::arg("threads") = 256,
         py::arg("reps") = 1);
+    /* the same for the bcast data phase (k_bcast_data): src is the root's
+     * buffer base (the kernel adds sl_b), dsts are already offset by the
+     * slice start. One dst: the zc_write = 0 form (my_out). Several: the
+     * push form, one entry per rank, 0 = skip (the root's own entry).
+     * Returns the milliseconds per launch. */
+    m.def(
+        "ec_bcast_data",
+        [](uintptr_t src, std::vector<uintptr_t> dsts, uint64_t sl_b,
+           uint64_t sl_e, int blocks, int threads, int reps) {
+            const size_t n = dsts.size();
+            if (src == 0 || n < 1 || n > (size_t)ucc::ec_hip::kMaxRanks ||
+                (n == 1 && dsts[0] == 0) || sl_e < sl_b || blocks < 1 ||
+                blocks > ucc::ec_hip::kGatedMaxBlocks || reps < 1) {
+                throw std::runtime_error("ec_bcast_data: bad arguments");
+            }
+            bool aligned = sl_b % 16 == 0 && src % 16 == 0;
+            for (uintptr_t q : dsts) {
+                aligned = aligned && q % 16 == 0;
+            }
+            if (!aligned) {
+                throw std::runtime_error("ec_bcast_data: pointers and sl_b "
+                                         "must be 16-byte aligned");
+            }
+            ucc::ec_hip::GatedArgs a{};
+            a.peer_in[0] = (const void *)src;
+            a.zc_write   = n > 1 ? 1 : 0;
+            if (a.zc_write) {
+                for (size_t r = 0; r < n; r++) {
+                    a.peer_out[r] = (const void *)dsts[r];
+                }
+            } else {
+                a.my_out = (void *)dsts[0];
+            }
+            a.sl_b    = sl_b;
+            a.sl_e    = sl_e;
+            a.nranks  = (int)n;
+            a.nblocks = blocks;
+            hipStream_t st = nullptr;
+            hipEvent_t  e0 = nullptr, e1 = nullptr;
+            if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) !=
+                    hipSuccess ||
+                hipEventCreate(&e0) != hipSuccess ||
+                hipEventCreate(&e1) != hipSuccess) {
+                if (e0) {
+                    (void)hipEventDestroy(e0);
+                }
+                if (st) {
+                    (void)hipStreamDestroy(st);
+                }
+                throw std::runtime_error("ec_bcast_data: no stream/events");
+            }
+            ucc_status_t rc = UCC_OK;
+            float        ms = 0.f;
+            (void)hipDeviceSynchronize();
+            (void)hipEventRecord(e0, st);
+            for (int i = 0; i < reps && rc == UCC_OK; i++) {
+                rc = ucc::ec_hip::bcast_data(a, st, threads);
+            }
+            (void)hipEventRecord(e1, st);
+            const hipError_t he = hipStreamSynchronize(st);
+            if (he == hipSuccess) {
+                (void)hipEventElapsedTime(&ms, e0, e1);
+            }
+            (void)hipEventDestroy(e0);
+            (void)hipEventDestroy(e1);
+            (void)hipStreamDestroy(st);
+            check(rc, "bcast_data");
+            if (he != hipSuccess) {
+                throw std::runtime_error(std::string("ec_bcast_data: ") +
+                                         hipGetErrorString(he));
+            }
+            return (double)ms / reps;
+        },
+        py::arg("src"), py::arg("dsts"), py::arg("sl_b"), py::arg("sl_e"),
+        py::arg("blocks"), py::arg("threads") = 256, py::arg("reps") = 1);
     /* kernel unit-test hook: one ring_step launch on the null stream,
      * in-process, synchronised. pieces: up to kMaxRings tuples
      * (in, local, out, dst, count), 0 = null pointer. Returns the status

@@ -258,6 +258,26 @@ ucc_status_t zc_data(const GatedArgs &a, hipStream_t s, int threads = 0);
  * on U (every U = 4 instantiation compiles to at least 2 waves/SIMD,
  * some U = 2 ones to 1). */
 int zc_depth(int nranks);
+/* Gated bcast, the copy-only slice phase (docs/GATED_PIPELINE.md "Rooted
+ * collectives"). All three move bytes [sl_b, sl_e) of ONE source,
+ * peer_in[0] + sl_b, in 16-byte packs: to my_out (zc_write = 0) or to
+ * every non-null peer_out[s], s < nranks (zc_write = 1; a null entry, the
+ * root's own, is skipped). peer_in[0] + sl_b and every destination must be
+ * 16-byte aligned; dt, op and alpha are ignored.
+ *  staged_bscatter: the launch staged_reduce is in the allreduce pattern
+ *    (waits stage and out-area reuse, signals phase 1 with the full grid;
+ *    host-target and derive mode).
+ *  zc_bcast: ONE launch per zero-copy post, the protocol and counter
+ *    effects of zc_allreduce with zc_write = 1 (phase 0 +1, phase 1
+ *    +nblocks, phase 2 +1) plus done_host/done_seq. Host-target mode and
+ *    zc_write = 1 only.
+ *  bcast_data: the data phase alone (k_bcast_data), no flag read or
+ *    written; uses peer_in[0], my_out / peer_out, sl_b, sl_e, nranks,
+ *    zc_write and nblocks and nothing else of `a`. threads: 64, 128 or
+ *    256 per block, 0 = 256. Measurement probe and unit-test hook. */
+ucc_status_t staged_bscatter(const GatedArgs &a, hipStream_t s);
+ucc_status_t zc_bcast(const GatedArgs &a, hipStream_t s);
+ucc_status_t bcast_data(const GatedArgs &a, hipStream_t s, int threads = 0);
 /* copy-engine gating (SDMA data path): pure wait on gw_phase/t_gather_wait
  * (1 block), and signal-phase-2-then-wait-team (full gated grid). */
 ucc_status_t gated_wait_only(const GatedArgs &a, hipStream_t s);

@@ -1,6 +1,7 @@
 /* gfx950 execution-component kernels: the device-gated family — staged
- * stage / reduce / gather, the copy-engine gates, and the fused zero-copy
- * allreduce (k_zc_allreduce). */
+ * stage / reduce / gather, the copy-engine gates, the fused zero-copy
+ * allreduce (k_zc_allreduce), and the copy-only slice phase of the rooted
+ * collectives (k_staged_bscatter, k_zc_bcast). */
 #include "ec_device.h"
 
 namespace ucc {
@@ -666,6 +667,140 @@ __global__ void __launch_bounds__(256) k_zc_data(const GatedArgs a)
     zc_data_phase<T, OP, VEC, U>(a);
 }
 
+/* ------------------------------------- rooted collectives: bcast phase */
+/* The data phase of the gated bcast, datatype-free: bytes [sl_b, sl_e) of
+ * ONE source (peer_in[0]: the root's in-area, or its user buffer in the
+ * zero-copy form) go to my_out (zc_write = 0: my out area, slice at
+ * offset 0, as k_staged_reduce leaves it) or to every non-null
+ * peer_out[s], s < nranks (zc_write = 1: push into the non-root ranks'
+ * buffers; the root's own entry is null and skipped). Source + sl_b and
+ * every destination are 16-byte aligned: areas are, sl_b is a multiple of
+ * 256, and the zero-copy consensus admits aligned user buffers only.
+ *
+ * 16-byte packs, U loads issued before the first store as in
+ * d_copy_bytes_part, each loaded pack stored to every destination, then a
+ * per-pack loop and a byte tail. U is a fixed 4, NOT the depth rule of
+ * the reduce kernels: that rule trades depth against the n sources a
+ * reduction holds in registers, and a copy has one source whatever n is,
+ * so 4 packs (64 B in flight per lane, d_copy_bytes_part's figure) cost
+ * 16 VGPRs at every team size. Nobody has measured another depth. */
+template <int U>
+__device__ __forceinline__ void bcast_phase(const GatedArgs &a)
+{
+    const uint64_t len = a.sl_e - a.sl_b;
+    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t str = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t nv  = len / 16;
+    const uint8_t *const src8 = (const uint8_t *)a.peer_in[0] + a.sl_b;
+    const uint4 *const   src  = (const uint4 *)src8;
+    /* read before any zc_write branch (see zc_data_phase) */
+    uint8_t *const out8 = (uint8_t *)a.my_out;
+    uint4 *const   out  = (uint4 *)out8;
+    const int      n    = a.nranks;
+    uint64_t       i    = tid;
+    for (; i + (U - 1) * str < nv; i += U * str) {
+        uint4 v[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            v[u] = src[i + (uint64_t)u * str];
+        }
+        if (a.zc_write) {
+#pragma unroll
+            for (int s = 0; s < kMaxRanks; s++) {
+                if (s < n && a.peer_out[s]) {
+                    uint4 *d = (uint4 *)a.peer_out[s];
+#pragma unroll
+                    for (int u = 0; u < U; u++) {
+                        d[i + (uint64_t)u * str] = v[u];
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                out[i + (uint64_t)u * str] = v[u];
+            }
+        }
+    }
+    for (; i < nv; i += str) {
+        const uint4 v = src[i];
+        if (a.zc_write) {
+#pragma unroll
+            for (int s = 0; s < kMaxRanks; s++) {
+                if (s < n && a.peer_out[s]) {
+                    ((uint4 *)a.peer_out[s])[i] = v;
+                }
+            }
+        } else {
+            out[i] = v;
+        }
+    }
+    for (uint64_t t = nv * 16 + tid; t < len; t += str) {
+        const uint8_t v = src8[t];
+        if (a.zc_write) {
+#pragma unroll
+            for (int s = 0; s < kMaxRanks; s++) {
+                if (s < n && a.peer_out[s]) {
+                    ((uint8_t *)a.peer_out[s])[t] = v;
+                }
+            }
+        } else {
+            out8[t] = v;
+        }
+    }
+}
+
+constexpr int kBcastDepth = 4;
+
+/* The slot k_staged_reduce has in the allreduce pattern, copy-only: wait
+ * for the team's stage of this fragment and for the out-area reuse, move
+ * my slice of the root's data, signal phase 1 with the full grid. */
+__global__ void k_staged_bscatter(const GatedArgs a)
+{
+    const GatedTargets gt = gated_targets(a);
+    if (!gated_wait(a, 0, gt.stage) ||
+        !gated_wait(a, 2, gt.prev_gather)) {
+        return;
+    }
+    bcast_phase<kBcastDepth>(a);
+    gated_signal(a, 1, gt.sig_reduce);
+}
+
+/* One launch per zero-copy bcast post (host-target mode only): entry and
+ * exit protocol of k_zc_allreduce with zc_write = 1, counter effects
+ * phase 0 +1, phase 1 +B, phase 2 +1. The entry wait on the team's phase
+ * 0 says that every rank has posted, so the non-root buffers may be
+ * written and the root's holds the message; the exit wait on the team's
+ * phase 1 says that every slice has landed in my buffer (non-root) and
+ * that nobody reads it any more (root). */
+__global__ void __launch_bounds__(256) k_zc_bcast(const GatedArgs a)
+{
+    if (blockIdx.x == 0) {
+        if (!zc_wait2(a, 1, a.t_sw_reduce, 2, a.t_sw_gather)) {
+            return;
+        }
+        gated_signal(a, 0, a.t_sig_stage, /*pub_done=*/false);
+    }
+    if (!zc_wait2(a, 0, a.t_stage, 2, a.t_prev_gather)) {
+        return;
+    }
+    bcast_phase<kBcastDepth>(a);
+    if (!gated_signal_last(a, 1, a.t_sig_reduce)) {
+        return;
+    }
+    if (!gated_wait(a, 1, a.t_gather_wait)) {
+        return;
+    }
+    gated_signal(a, 2, a.t_sig_gather, /*pub_done=*/true);
+}
+
+/* bcast_phase alone, for measurement and unit tests: no flags, no waits,
+ * no signals (the k_zc_data of the bcast). */
+__global__ void __launch_bounds__(256) k_bcast_data(const GatedArgs a)
+{
+    bcast_phase<kBcastDepth>(a);
+}
+
 /* ----------------------------------------------------------- launchers */
 static inline int gated_grid(const GatedArgs &a)
 {
@@ -833,6 +968,36 @@ ucc_status_t zc_data(const GatedArgs &a, hipStream_t s, int threads)
     const ZcDataLaunch l{a, threads ? threads : zc_threads()};
     return dispatch<LaunchZcData>(fold_complex(a.dt, a.op, nullptr), a.op,
                                   l, s);
+}
+
+ucc_status_t staged_bscatter(const GatedArgs &a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_staged_bscatter, dim3(gated_grid(a)), dim3(256), 0,
+                       s, a);
+    return launch_status();
+}
+
+ucc_status_t zc_bcast(const GatedArgs &a, hipStream_t s)
+{
+    if (a.derive || !a.zc_write || a.nranks < 2 || a.nranks > kMaxRanks ||
+        a.sl_e < a.sl_b) {
+        return UCC_ERR_NOT_SUPPORTED; /* host-target push form only */
+    }
+    hipLaunchKernelGGL(k_zc_bcast, dim3(gated_grid(a)), dim3(256), 0, s, a);
+    return launch_status();
+}
+
+ucc_status_t bcast_data(const GatedArgs &a, hipStream_t s, int threads)
+{
+    if (a.nranks < 1 || a.nranks > kMaxRanks || a.sl_e < a.sl_b ||
+        !a.peer_in[0] || (!a.zc_write && !a.my_out) ||
+        (threads != 0 && threads != 64 && threads != 128 &&
+         threads != 256)) {
+        return UCC_ERR_INVALID_PARAM;
+    }
+    hipLaunchKernelGGL(k_bcast_data, dim3(gated_grid(a)),
+                       dim3(threads ? threads : 256), 0, s, a);
+    return launch_status();
 }
 
 } // namespace ec_hip

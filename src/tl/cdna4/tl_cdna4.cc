@@ -102,6 +102,7 @@ struct Cdna4Cfg {
     bool     p2p;        /* device active-set bcast (p2p send/recv)      */
     uint32_t p2p_depth;  /* mailbox ring depth, power of two <= 64       */
     int      p2p_blocks; /* pull kernel grid size; 0 = size-derived      */
+    bool     gated_rooted; /* gated_pipeline for full-team bcast/reduce  */
     bool     ring;       /* offer the multi-ring algorithms              */
     int      ring_nrings; /* rings to use, 0 = auto (ring_plan.h)        */
 };
@@ -1470,7 +1471,9 @@ class GatedCollTask final : public Cdna4Task {
             (ct_ == UCC_COLL_TYPE_ALLREDUCE ||
              ct_ == UCC_COLL_TYPE_REDUCE_SCATTER ||
              ct_ == UCC_COLL_TYPE_ALLGATHER ||
-             ct_ == UCC_COLL_TYPE_ALLTOALL) &&
+             ct_ == UCC_COLL_TYPE_ALLTOALL ||
+             ct_ == UCC_COLL_TYPE_BCAST ||
+             ct_ == UCC_COLL_TYPE_REDUCE) &&
             Config::instance().get_bool("TL_CDNA4", "ZCOPY", true)) {
             if (a_.flags & UCC_COLL_ARGS_FLAG_PERSISTENT) {
                 zc_ = true; /* exchange amortized over re-posts */
@@ -1513,7 +1516,11 @@ class GatedCollTask final : public Cdna4Task {
         }
         if (pslot_ < 0) {
             ucc_coll_type_t k_ct = a_.coll_type;
-            int kind = k_ct == UCC_COLL_TYPE_ALLREDUCE
+            /* bcast and reduce always run the staged allreduce launch
+             * pattern here (three kernels of B blocks per iteration) */
+            int kind = (k_ct == UCC_COLL_TYPE_ALLREDUCE ||
+                        k_ct == UCC_COLL_TYPE_BCAST ||
+                        k_ct == UCC_COLL_TYPE_REDUCE)
                            ? Cdna4TlTeam::PK_G_AR
                        : (k_ct == UCC_COLL_TYPE_REDUCE_SCATTER ||
                           k_ct == UCC_COLL_TYPE_REDUCE_SCATTERV)
@@ -1566,6 +1573,38 @@ class GatedCollTask final : public Cdna4Task {
             total_ = a_.dst.info.count * dtsz_;
             dbuf_  = (uint8_t *)a_.dst.info.buffer;
             sbuf_  = inplace ? dbuf_ : (const uint8_t *)a_.src.info.buffer;
+            break;
+        case UCC_COLL_TYPE_BCAST:
+            /* fragments and slices of allreduce; one buffer is source
+             * (root) and destination (everyone else) */
+            if (a_.root >= n_) {
+                return UCC_ERR_INVALID_PARAM;
+            }
+            dt_    = a_.src.info.datatype;
+            dtsz_  = ucc_dt_size(dt_);
+            total_ = a_.src.info.count * dtsz_;
+            dbuf_  = (uint8_t *)a_.src.info.buffer;
+            sbuf_  = dbuf_;
+            break;
+        case UCC_COLL_TYPE_REDUCE:
+            /* dst.info is valid at the root only. A non-root rank has no
+             * destination: dbuf_ stays null there and no launch is ever
+             * handed it (empty gather slices; zero-copy writes go to the
+             * ROOT's mapped dst). */
+            if (a_.root >= n_) {
+                return UCC_ERR_INVALID_PARAM;
+            }
+            dt_    = a_.src.info.datatype;
+            dtsz_  = ucc_dt_size(dt_);
+            total_ = a_.src.info.count * dtsz_;
+            if (me_ == (uint32_t)a_.root) {
+                dbuf_ = (uint8_t *)a_.dst.info.buffer;
+                sbuf_ = inplace ? dbuf_
+                                : (const uint8_t *)a_.src.info.buffer;
+            } else {
+                dbuf_ = nullptr;
+                sbuf_ = (const uint8_t *)a_.src.info.buffer;
+            }
             break;
         case UCC_COLL_TYPE_REDUCE_SCATTER: {
             dt_   = a_.dst.info.datatype;
@@ -1787,6 +1826,10 @@ class GatedCollTask final : public Cdna4Task {
             if (!all_ge(0)) {
                 return UCC_INPROGRESS;
             }
+            /* what is exported as "my destination": a rank without one
+             * (non-root reduce) exports its source again, which takes
+             * the same-allocation route below and is never written */
+            uint8_t *const xd = dbuf_ ? dbuf_ : (uint8_t *)sbuf_;
             ZcBlob b{};
             b.magic = 0x5a43;
             /* registered-buffer fast path (reference
@@ -1808,10 +1851,10 @@ class GatedCollTask final : public Cdna4Task {
                 if ((a_.mask &
                      UCC_COLL_ARGS_FIELD_MEM_MAP_DST_MEMH) &&
                     a_.dst_memh &&
-                    ucc_memh_lookup(a_.dst_memh, dbuf_, total_, &b.hd,
+                    ucc_memh_lookup(a_.dst_memh, xd, total_, &b.hd,
                                     &doff)) {
                     b.d_base_off = doff;
-                    b.d_raw_ptr  = (uint64_t)(uintptr_t)dbuf_;
+                    b.d_raw_ptr  = (uint64_t)(uintptr_t)xd;
                     b.pad        = 0;
                 } else {
                     /* dst not registered: fall through to the runtime
@@ -1819,13 +1862,13 @@ class GatedCollTask final : public Cdna4Task {
                     hipDeviceptr_t dbase  = nullptr;
                     size_t         dbsize = 0;
                     if (hipMemGetAddressRange(&dbase, &dbsize,
-                                              (hipDeviceptr_t)dbuf_) ==
+                                              (hipDeviceptr_t)xd) ==
                             hipSuccess &&
                         hipIpcGetMemHandle(&b.hd, (void *)dbase) ==
                             hipSuccess) {
-                        b.d_base_off = (uint64_t)((uintptr_t)dbuf_ -
+                        b.d_base_off = (uint64_t)((uintptr_t)xd -
                                                   (uintptr_t)dbase);
-                        b.d_raw_ptr  = (uint64_t)(uintptr_t)dbuf_;
+                        b.d_raw_ptr  = (uint64_t)(uintptr_t)xd;
                         b.pad        = 0;
                     } else {
                         b.magic = 0;
@@ -1861,13 +1904,13 @@ class GatedCollTask final : public Cdna4Task {
                     /* CE a2av pulls from peers' src into LOCAL dst:
                      * no dst export needed */
                 } else if (hipMemGetAddressRange(&dbase, &dbsize,
-                                          (hipDeviceptr_t)dbuf_) ==
+                                          (hipDeviceptr_t)xd) ==
                         hipSuccess &&
                     hipIpcGetMemHandle(&b.hd, (void *)dbase) ==
                         hipSuccess) {
                     b.d_base_off =
-                        (uint64_t)((uintptr_t)dbuf_ - (uintptr_t)dbase);
-                    b.d_raw_ptr = (uint64_t)(uintptr_t)dbuf_;
+                        (uint64_t)((uintptr_t)xd - (uintptr_t)dbase);
+                    b.d_raw_ptr = (uint64_t)(uintptr_t)xd;
                     b.pad = (dbase == base) ? 1 : 0; /* same alloc */
                 } else {
                     b.magic = 0; /* dst export failed: fall back */
@@ -2215,7 +2258,20 @@ class GatedCollTask final : public Cdna4Task {
             !derive) {
             return enqueue_ce_a2av(comp_s);
         }
-        if (zc_ && zc_ready_ && nfrags_ > 1 &&
+        /* bcast / reduce: a triggered post always runs the staged
+         * pattern (their zero-copy patterns launch other kernel counts
+         * per iteration, the staged one keeps PK_G_AR's pp = 3), so
+         * zero-copy state from an earlier host post is ignored and the
+         * chunk-sized fragments come back */
+        const bool rooted = ct_ == UCC_COLL_TYPE_BCAST ||
+                            ct_ == UCC_COLL_TYPE_REDUCE;
+        const bool rzc    = rooted && zc_ && zc_ready_ && !derive;
+        if (rooted && derive && gran_ != tt_->cfg_.chunk) {
+            gran_   = tt_->cfg_.chunk;
+            nfrags_ = (total_ + gran_ - 1) / gran_;
+            nfrags_ = nfrags_ ? nfrags_ : 1;
+        }
+        if (zc_ && zc_ready_ && nfrags_ > 1 && !(rooted && derive) &&
             Config::instance().get_bool("TL_CDNA4", "ZC_DEFRAG", true)) {
             /* zero-copy reads/writes USER buffers only — no staging
              * area is touched, so the chunk-size bound (the only reason
@@ -2235,7 +2291,7 @@ class GatedCollTask final : public Cdna4Task {
         const bool zc_fused =
             zc_ && zc_ready_ && nfrags_ == 1 && !derive &&
             (ct_ == UCC_COLL_TYPE_ALLREDUCE ||
-             ct_ == UCC_COLL_TYPE_REDUCE_SCATTER) &&
+             ct_ == UCC_COLL_TYPE_REDUCE_SCATTER || rooted) &&
             Config::instance().get_bool("TL_CDNA4", "ZC_FUSED", true);
         /* grid size, measured on the 2-proc rig. 64 blocks by default.
          * One-kernel allreduce of 2 ranks at depth 4, the one case
@@ -2298,9 +2354,11 @@ class GatedCollTask final : public Cdna4Task {
                 const bool is_rs =
                     ct_ == UCC_COLL_TYPE_REDUCE_SCATTER ||
                     ct_ == UCC_COLL_TYPE_REDUCE_SCATTERV;
+                const bool ar_pat =
+                    ct_ == UCC_COLL_TYPE_ALLREDUCE || rooted;
                 ga.derive     = 1;
-                ga.pp         = ct_ == UCC_COLL_TYPE_ALLREDUCE ? 3 : 2;
-                ga.has_reduce = ct_ == UCC_COLL_TYPE_ALLREDUCE || is_rs;
+                ga.pp         = ar_pat ? 3 : 2;
+                ga.has_reduce = ar_pat || is_rs;
                 ga.has_gather = !is_rs;
             }
             ucc_status_t st = UCC_OK;
@@ -2382,6 +2440,166 @@ class GatedCollTask final : public Cdna4Task {
                     }
                     ec_hip::GatedArgs gg = ga;
                     gg.nblocks           = (int)Bg;
+                    if (!derive && f == nfrags_ - 1) {
+                        gg.done_host = tt_->gdone_host_ + slot_;
+                        gg.done_seq  = done_seq_;
+                    }
+                    st = ec_hip::staged_gather(gg, comp_s);
+                    if (!derive) { L[2][slot_][p] += Bg; }
+                }
+                break;
+            }
+            case UCC_COLL_TYPE_REDUCE:
+            case UCC_COLL_TYPE_BCAST: {
+                /* Rooted collectives as sub-patterns of the allreduce
+                 * (docs/GATED_PIPELINE.md "Rooted collectives"): same
+                 * fragments, same slices, and on every rank, whatever
+                 * the root, the same launches with the same grids, so
+                 * the ledger stays symmetric.
+                 *  reduce = allreduce in which only the root gathers;
+                 *  bcast  = allreduce with one contributor: rank r takes
+                 *           slice r from the root, slices are exchanged. */
+                const uint32_t root    = (uint32_t)a_.root;
+                const bool     is_root = me_ == root;
+                const bool     bc      = ct_ == UCC_COLL_TYPE_BCAST;
+                ga.src = sbuf_ + off;
+                ga.dst = dbuf_ ? dbuf_ + off : nullptr;
+                size_t per = (len / n_) & ~(size_t)255;
+                for (uint32_t r = 0; r < n_; r++) {
+                    ga.slice_b[r] = (uint64_t)r * per;
+                    ga.slice_e[r] =
+                        r == n_ - 1 ? len : (uint64_t)(r + 1) * per;
+                }
+                ga.sl_b = ga.slice_b[me_];
+                ga.sl_e = ga.slice_e[me_];
+                if (rzc && !bc) {
+                    /* zero-copy reduce: the reduce_scatter form. Rank r
+                     * reduces slice r of every rank's user src straight
+                     * into the ROOT's dst; completion = the team's
+                     * reduces are done (root: dst complete; everyone: src
+                     * no longer read). In place at the root each slice
+                     * is read, then written, by its owner only. */
+                    ga.len    = 0;
+                    ga.my_out = zc_peer_dst_[root] + off + ga.sl_b;
+                    for (uint32_t r = 0; r < n_; r++) {
+                        ga.peer_in[r] = zc_peer_src_[r] + off;
+                    }
+                    ga.t_sw_reduce   = L[1][slot_][p];
+                    ga.t_sw_gather   = L[2][slot_][p];
+                    ga.t_prev_gather = 0;
+                    ga.t_stage       = L[0][slot_][p] + 1;
+                    ga.t_sig_stage   = L[0][slot_][p] + 1;
+                    ga.t_sig_reduce  = L[1][slot_][p] + B;
+                    if (zc_fused) {
+                        log_path("one-kernel (k_zc_allreduce into the "
+                                 "root's dst)", nblk);
+                        ga.t_gather_wait = L[1][slot_][p] + B;
+                        ga.done_host     = tt_->gdone_host_ + slot_;
+                        ga.done_seq      = done_seq_;
+                        st = ec_hip::zc_allreduce(ga, comp_s);
+                        L[0][slot_][p] += 1;
+                        L[1][slot_][p] += B;
+                        break;
+                    }
+                    log_path("three-kernel (stage/reduce/wait into the "
+                             "root's dst)", nblk);
+                    {
+                        ec_hip::GatedArgs gs = ga;
+                        gs.nblocks           = 1;
+                        st = ec_hip::staged_stage(gs, stage_s);
+                    }
+                    L[0][slot_][p] += 1;
+                    if (st == UCC_OK) {
+                        st = ec_hip::staged_reduce(ga, comp_s);
+                        L[1][slot_][p] += B;
+                    }
+                    if (st == UCC_OK && f == nfrags_ - 1) {
+                        ec_hip::GatedArgs gw = ga;
+                        gw.gw_phase          = 1;
+                        gw.t_gather_wait     = L[1][slot_][p];
+                        gw.done_host         = tt_->gdone_host_ + slot_;
+                        gw.done_seq          = done_seq_;
+                        st = ec_hip::gated_wait_only(gw, comp_s);
+                    }
+                    break;
+                }
+                if (rzc) {
+                    /* zero-copy bcast, push: rank r reads slice r of the
+                     * root's user buffer and writes it into every
+                     * non-root rank's buffer at the same offset (the
+                     * root's own entry stays null: skipped) */
+                    ga.len        = 0;
+                    ga.zc_write   = 1;
+                    ga.peer_in[0] = zc_peer_src_[root] + off;
+                    for (uint32_t r = 0; r < n_; r++) {
+                        ga.peer_out[r] =
+                            r == root ? nullptr
+                                      : (const void *)(zc_peer_dst_[r] +
+                                                       off + ga.sl_b);
+                    }
+                }
+                /* allreduce targets and increments: full grids when
+                 * staged (and always in derive mode), one block for the
+                 * pure signal / pure wait of the zero-copy form */
+                const uint64_t Bs = rzc ? 1 : B;
+                const uint64_t Bg = Bs;
+                ga.t_sw_reduce   = L[1][slot_][p];
+                ga.t_sw_gather   = L[2][slot_][p];
+                ga.t_prev_gather = L[2][slot_][p];
+                ga.t_stage       = L[0][slot_][p] + Bs;
+                ga.gw_phase      = 1;
+                ga.t_gather_wait = L[1][slot_][p] + B;
+                ga.t_sig_stage   = L[0][slot_][p] + Bs;
+                ga.t_sig_reduce  = L[1][slot_][p] + B;
+                ga.t_sig_gather  = L[2][slot_][p] + Bg;
+                if (rzc && zc_fused) {
+                    log_path("one-kernel (k_zc_bcast)", nblk);
+                    ga.done_host = tt_->gdone_host_ + slot_;
+                    ga.done_seq  = done_seq_;
+                    st = ec_hip::zc_bcast(ga, comp_s);
+                    L[0][slot_][p] += 1;
+                    L[1][slot_][p] += B;
+                    L[2][slot_][p] += 1;
+                    break;
+                }
+                if (rzc) {
+                    log_path("three-kernel (stage/bscatter/wait)", nblk);
+                }
+                {
+                    /* staged: every rank of a reduce stages its fragment,
+                     * of a bcast the root alone (the others only signal) */
+                    ec_hip::GatedArgs gs = ga;
+                    gs.nblocks           = (int)Bs;
+                    if (!rzc && bc && !is_root) {
+                        gs.len = 0;
+                    }
+                    st = ec_hip::staged_stage(gs, stage_s);
+                }
+                if (!derive) { L[0][slot_][p] += Bs; }
+                if (st == UCC_OK) {
+                    if (bc) {
+                        ec_hip::GatedArgs gb = ga;
+                        if (!rzc) {
+                            /* my slice of the ROOT's in-area -> my out */
+                            gb.peer_in[0] = tt_->area(root, slot_, p, 0);
+                        }
+                        st = ec_hip::staged_bscatter(gb, comp_s);
+                    } else {
+                        st = ec_hip::staged_reduce(ga, comp_s);
+                    }
+                    if (!derive) { L[1][slot_][p] += B; }
+                }
+                if (st == UCC_OK) {
+                    /* who gathers: of a reduce the root, of a bcast
+                     * everyone else; all other launches (and all of the
+                     * zero-copy form) are wait + signal only */
+                    ec_hip::GatedArgs gg = ga;
+                    gg.nblocks           = (int)Bg;
+                    if (rzc || (bc ? is_root : !is_root)) {
+                        for (uint32_t r = 0; r < n_; r++) {
+                            gg.slice_e[r] = gg.slice_b[r];
+                        }
+                    }
                     if (!derive && f == nfrags_ - 1) {
                         gg.done_host = tt_->gdone_host_ + slot_;
                         gg.done_seq  = done_seq_;
@@ -3246,6 +3464,13 @@ class Cdna4Tl final : public Tl {
                     "rings of the 'ring' algorithm, one per stride coprime "
                     "to the team size, at most 4 (0 = auto: "
                     "min(4, phi(n)); must match on every rank)");
+        cfg.declare("TL_CDNA4", "GATED_ROOTED", "0",
+                    "serve full-team device bcast and reduce with the "
+                    "device-gated pipeline (algorithm 'gated_pipeline', "
+                    "score 90: scatter + allgather resp. slice reduce + "
+                    "gather at the root, zero-copy for persistent and "
+                    "large requests) instead of staged_linear; must be "
+                    "the same on every rank");
         if (!cfg.get_bool("TL_CDNA4", "ENABLE", true) ||
             !mc::hip_available()) {
             return nullptr;
@@ -3298,6 +3523,7 @@ class Cdna4Tl final : public Tl {
         if (c.p2p_blocks > ec_hip::kP2pMaxBlocks) {
             c.p2p_blocks = ec_hip::kP2pMaxBlocks;
         }
+        c.gated_rooted = cfg.get_bool("TL_CDNA4", "GATED_ROOTED", false);
         c.ring        = cfg.get_bool("TL_CDNA4", "RING", false);
         c.ring_nrings = (int)cfg.get_int("TL_CDNA4", "RING_NRINGS", 0);
         if (c.ring_nrings < 0) {
@@ -3341,6 +3567,10 @@ void Cdna4TlTeam::get_scores(Team *team, ScoreMap &map)
                 if (!ec_hip::op_supported(gdt, args.op)) {
                     return UCC_ERR_NOT_SUPPORTED;
                 }
+            }
+            if (args.coll_type == UCC_COLL_TYPE_REDUCE &&
+                !ec_hip::op_supported(args.src.info.datatype, args.op)) {
+                return UCC_ERR_NOT_SUPPORTED;
             }
             /* in-process multi-rank jigs can serialize spinning kernels
              * on one HW queue: host-gated staged path is the safe
@@ -3451,6 +3681,12 @@ void Cdna4TlTeam::get_scores(Team *team, ScoreMap &map)
         add_gated(UCC_COLL_TYPE_ALLGATHERV, 0, SIZE_MAX, 90);
         add_gated(UCC_COLL_TYPE_ALLTOALL, 0, SIZE_MAX, 90);
         add_gated(UCC_COLL_TYPE_ALLTOALLV, 0, SIZE_MAX, 90);
+        if (cfg_.gated_rooted) {
+            /* opt-in (UCC_TL_CDNA4_GATED_ROOTED): unset, bcast and reduce
+             * keep exactly the staged_linear entries below */
+            add_gated(UCC_COLL_TYPE_BCAST, 0, SIZE_MAX, 90);
+            add_gated(UCC_COLL_TYPE_REDUCE, 0, SIZE_MAX, 90);
+        }
     }
     add(UCC_COLL_TYPE_ALLREDUCE, 0, SIZE_MAX, 80, "staged_linear", false);
     add(UCC_COLL_TYPE_ALLGATHER, 0, SIZE_MAX, 80, "staged_linear", false);

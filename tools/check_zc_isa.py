@@ -13,6 +13,11 @@ produces them) and fails unless
     blocks of 256 threads per CU: the residency arithmetic behind the
     192-block grid in src/tl/cdna4/tl_cdna4.cc.
 
+The unit also holds the one-kernel zero-copy bcast:
+
+ 4. k_zc_bcast (not a template: one instantiation) uses no scratch memory
+    either.
+
 Occupancy is the compiler's figure, VGPRs and AGPRs together."""
 
 import re
@@ -20,6 +25,7 @@ import sys
 
 NAME = re.compile(r"k_zc_allreduceI(.+?)Li(\d+)ELi(\d+)ELi(\d+)EEEv")
 FLAGSHIP = ("NS0_6bf16_tE", 0, 8, 4)
+BCAST = re.compile(r"10k_zc_bcastE")
 
 
 def parse(text):
@@ -39,6 +45,23 @@ def parse(text):
                         scratch=field(r"ScratchSize \[bytes/lane\]"),
                         waves=field(r"Occupancy \[waves/SIMD\]"))
     return out
+
+
+def parse_bcast(text):
+    """ScratchSize of every k_zc_bcast remark block (one is expected)."""
+    out = []
+    for blk in re.split(r"(?=remark: [^\n]*Function Name: )", text):
+        m = re.search(r"Function Name: (\S+)", blk)
+        if m and BCAST.search(m.group(1)):
+            out.append(int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)",
+                                     blk).group(1)))
+    return out
+
+
+def check_bcast(scratch):
+    if not scratch:
+        return ["k_zc_bcast not found"]
+    return [f"k_zc_bcast: {s} B/lane of scratch" for s in scratch if s]
 
 
 def check(kernels):
@@ -62,7 +85,7 @@ def check(kernels):
 def main():
     text = open(sys.argv[1]).read() if len(sys.argv) > 1 else sys.stdin.read()
     kernels = parse(text)
-    bad = check(kernels)
+    bad = check(kernels) + check_bcast(parse_bcast(text))
     for b in bad:
         print("check_zc_isa:", b)
     if bad:
@@ -71,7 +94,8 @@ def main():
     low = min(k["waves"] for key, k in kernels.items() if key[3] == 4)
     print(f"check_zc_isa ok: {len(kernels)} k_zc_allreduce instantiations, "
           f"no scratch; flagship {f['vgprs']} VGPRs, {f['waves']} "
-          f"waves/SIMD; depth 4 at least {low} waves/SIMD")
+          f"waves/SIMD; depth 4 at least {low} waves/SIMD; k_zc_bcast no "
+          f"scratch")
     return 0
 
 
