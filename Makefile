@@ -41,7 +41,7 @@ SHLIB  := $(BUILD)/libucc_amd.so
 PERFTEST := build/ucc_perftest
 INFO     := build/ucc_info
 NTESTS   := build/test_generic_dt build/test_obj_size build/test_mt \
-            build/test_p2p_mbox build/test_ring_plan
+            build/test_p2p_mbox build/test_ring_plan build/test_fused_plan
 
 all: $(MODULE) $(SHLIB) $(PERFTEST) $(INFO) $(NTESTS)
 
@@ -64,6 +64,10 @@ build/test_p2p_mbox: $(BUILD)/tests/test_p2p_mbox.o
 
 # host-only: the ring schedule header and nothing else of the library
 build/test_ring_plan: $(BUILD)/tests/test_ring_plan.o
+	$(HIPCC) $^ -o $@
+
+# host-only: the fused-collective plan header and nothing else of the library
+build/test_fused_plan: $(BUILD)/tests/test_fused_plan.o
 	$(HIPCC) $^ -o $@
 
 $(BUILD)/tools/%.o: tools/%.cc tools/shm_oob.h
@@ -158,11 +162,16 @@ build/asan_ring_plan: tests/native/test_ring_plan.cc src/tl/cdna4/ring_plan.h
 	$(HIPCC) -x c++ -std=c++17 -O1 -g -fsanitize=address,undefined \
 	    -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< -o $@
 
+build/asan_fused_plan: tests/native/test_fused_plan.cc src/tl/cdna4/fused_plan.h
+	$(HIPCC) -x c++ -std=c++17 -O1 -g -fsanitize=address,undefined \
+	    -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< -o $@
+
 .PHONY: asan
 asan: build/asan_generic_dt build/asan_obj_size build/asan_perftest \
-      build/asan_p2p_mbox build/asan_ring_plan
+      build/asan_p2p_mbox build/asan_ring_plan build/asan_fused_plan
 	ASAN_OPTIONS=detect_leaks=1 ./build/asan_p2p_mbox
 	ASAN_OPTIONS=detect_leaks=1 ./build/asan_ring_plan
+	ASAN_OPTIONS=detect_leaks=1 ./build/asan_fused_plan
 	ASAN_OPTIONS=detect_leaks=1 ./build/asan_obj_size
 	ASAN_OPTIONS=detect_leaks=1 ./build/asan_generic_dt
 	for cl in allreduce bcast alltoall alltoallv reduce_scatter barrier; do \

@@ -116,6 +116,55 @@ struct GraphFusedArgs {
 ucc_status_t fused_allreduce_graph(const GraphFusedArgs &a,
                                    hipStream_t stream);
 
+/* Fused small-message allgather / reduce_scatter / alltoall / bcast /
+ * reduce: the fused allreduce's protocol on the same flag words and
+ * counters (so both compose on one slot sequence), with what is staged and
+ * what is read given by a plan (src/tl/cdna4/fused_plan.h):
+ *   1. copy n_cells cells src + c_src_off[k] -> my_scratch + c_sc_off[k]
+ *   2. handshake with every rank (every rank, also one with no cell and
+ *      no segment)
+ *   3. copy n_segs segments peer_scratch[g_peer[k]] + g_sc_off[k] ->
+ *      dst + g_dst_off[k]; and, when r_count != 0, reduce r_count elements
+ *      at r_sc_off of all nranks scratch areas, ranks 0..n-1 in order, into
+ *      dst + r_dst_off (dtype x op as in reduce(); op 12 is SUM with
+ *      alpha).
+ * Every scratch offset is a multiple of 16. src and dst may have any
+ * alignment: an access whose user side is not 16-byte aligned goes byte by
+ * byte resp. element by element, and no access falls outside a cell or a
+ * segment. dt and op matter only when r_count != 0.
+ *
+ * fused_coll(): host-sequenced, the FusedArgs fields seq / stage_target /
+ * spin_limit / done_*. fused_coll_graph(): iteration number from the
+ * per-block launch counters and parity staging as in GraphFusedArgs; the
+ * host-sequencing fields are ignored. */
+struct FusedCollArgs {
+    const void *src;
+    void       *dst;
+    void       *my_scratch;
+    const void *peer_scratch[kMaxRanks];
+    uint64_t   *local_flags;
+    uint64_t   *peer_flags[kMaxRanks];
+    int         rank, nranks, slot;
+    int         n_cells, n_segs;
+    uint64_t    c_src_off[kMaxRanks], c_sc_off[kMaxRanks], c_len[kMaxRanks];
+    int         g_peer[kMaxRanks];
+    uint64_t    g_sc_off[kMaxRanks], g_dst_off[kMaxRanks], g_len[kMaxRanks];
+    uint64_t    r_sc_off, r_dst_off, r_count;
+    ucc_datatype_t     dt;
+    ucc_reduction_op_t op;
+    double      alpha;
+    uint64_t   *error_word;
+    int         nblocks;      /* graph: <= kMaxGraphBlocks                 */
+    /* host-sequenced only */
+    uint64_t    seq, stage_target, spin_limit;
+    uint64_t   *done_host;
+    uint64_t    done_seq, done_target;
+    /* graph only */
+    uint64_t    parity_stride;
+};
+ucc_status_t fused_coll(const FusedCollArgs &a, hipStream_t stream);
+ucc_status_t fused_coll_graph(const FusedCollArgs &a, hipStream_t stream);
+
 bool dt_supported(ucc_datatype_t dt);
 bool op_supported(ucc_datatype_t dt, ucc_reduction_op_t op);
 

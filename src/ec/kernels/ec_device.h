@@ -666,6 +666,130 @@ __device__ __forceinline__ bool spin_until(const uint64_t *f,
     return true;
 }
 
+/* ------------------------------------------ fused one-kernel protocol  */
+/* The sequencing, handshake and completion steps shared by the fused
+ * small-message kernels (ec_fused.hip: allreduce; ec_fused_colls.hip: the
+ * other collectives). All of them run on the same flag words and counters
+ * of a slot, so they compose on one slot sequence.
+ *
+ * DEV_SEQ = false (FusedArgs-style fields): the host tracks the sequence
+ * number, the cumulative stage target and the spin limit, and may ask for
+ * the host-visible completion word.
+ * DEV_SEQ = true (GraphFusedArgs-style fields): the iteration number is
+ * this block's launch count, so one captured launch replays as a new
+ * collective each time; staging alternates between two parity areas; the
+ * spin cap is the default. */
+struct FusedIter {
+    uint64_t seq, par, stage_target, cap;
+};
+
+template <bool DEV_SEQ, typename Args>
+__device__ __forceinline__ FusedIter fused_iter(const Args &a)
+{
+    FusedIter it;
+    if constexpr (DEV_SEQ) {
+        /* 0. device-side iteration number: this block's launch count.
+         * Every block of every launch/replay increments its own counter
+         * exactly once, so all blocks of one launch observe the same
+         * value. */
+        uint64_t *my_cnt = a.local_flags + kGraphCntBase +
+                           (uint64_t)a.slot * kMaxGraphBlocks + blockIdx.x;
+        __shared__ uint64_t s_seq;
+        if (threadIdx.x == 0) {
+            s_seq = __hip_atomic_fetch_add(my_cnt, 1, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT) +
+                    1;
+        }
+        __syncthreads();
+        it.seq          = s_seq;
+        it.par          = (it.seq & 1) * a.parity_stride;
+        it.stage_target = it.seq * (uint64_t)a.nblocks;
+        it.cap          = kSpinLimit;
+    } else {
+        it.seq          = a.seq;
+        it.par          = 0;
+        it.stage_target = a.stage_target;
+        it.cap          = spin_cap(a.spin_limit);
+    }
+    return it;
+}
+
+/* Called by every thread once its staging stores are issued. Publishes the
+ * staged data, signals every peer and waits for all ranks. false: a spin
+ * timed out (error_word is set); all threads of the block get the same
+ * answer and must leave. */
+template <typename Args>
+__device__ __forceinline__ bool fused_handshake(const Args &a,
+                                                const FusedIter &it)
+{
+    __threadfence_system();
+    __syncthreads();
+    /* 2. grid arrival: each block bumps the staging counter; block 0
+     * waits for all blocks, then signals every peer (incl. self) with seq.
+     * The staging counter (u64 index kStageCntBase + slot) is monotone and
+     * grows by nblocks per use -> target seq*nblocks. */
+    uint64_t *stage_cnt = a.local_flags + kStageCntBase + a.slot;
+    __shared__ int s_err;
+    if (threadIdx.x == 0) {
+        s_err = 0;
+        __hip_atomic_fetch_add(stage_cnt, 1, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (blockIdx.x == 0) {
+        if (threadIdx.x == 0 &&
+            !spin_until(stage_cnt, it.stage_target, it.cap, a.error_word)) {
+            s_err = 1;
+        }
+        __syncthreads();
+        if (!s_err && (int)threadIdx.x < a.nranks) {
+            sys_store(a.peer_flags[threadIdx.x] +
+                          (uint64_t)a.slot * kMaxRanks + a.rank,
+                      it.seq);
+        }
+    }
+    /* 3. all blocks wait for all ranks' arrivals (timeout: all threads
+     * leave together — never return while siblings sit at a barrier) */
+    if (!s_err && (int)threadIdx.x < a.nranks &&
+        !spin_until(a.local_flags + (uint64_t)a.slot * kMaxRanks +
+                        threadIdx.x,
+                    it.seq, it.cap, a.error_word)) {
+        s_err = 1;
+    }
+    __syncthreads();
+    if (s_err) {
+        return false;
+    }
+    __threadfence_system(); /* acquire: drop stale lines before peer reads */
+    return true;
+}
+
+/* 5. host-visible completion: the last arriving block publishes
+ * done_seq to the pinned word — the host polls plain memory
+ * instead of event record+query (see FusedArgs.done_host). dst
+ * stores are fenced before the arrival add; the release store
+ * makes them visible to the host with the flag. */
+template <typename Args>
+__device__ __forceinline__ void fused_publish_done(const Args &a)
+{
+    if (a.done_host) {
+        __threadfence_system();
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint64_t v = __hip_atomic_fetch_add(
+                             a.local_flags + kFusedDoneBase + a.slot, 1,
+                             __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) +
+                         1;
+            if (v == a.done_target) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __hip_atomic_store(a.done_host, a.done_seq,
+                                   __ATOMIC_RELEASE,
+                                   __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
+    }
+}
+
 /* ------------------------------------------------------------ dispatch  */
 /* THE dtype x op table. L<T, OP>::run(a, s) is a launcher; OP ids match
  * ucc_reduction_op_t. Float types take SUM PROD MAX MIN AVG, integer

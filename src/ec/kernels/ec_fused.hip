@@ -23,31 +23,8 @@ template <typename T, int OP, int VEC, bool DEV_SEQ, typename Args>
 __device__ __forceinline__ void fused_body(const Args &a)
 {
     using P = Pack<T, OP, VEC>;
-    uint64_t seq, par, stage_target, cap;
-    if constexpr (DEV_SEQ) {
-        /* 0. device-side iteration number: this block's launch count.
-         * Every block of every launch/replay increments its own counter
-         * exactly once, so all blocks of one launch observe the same
-         * value. */
-        uint64_t *my_cnt = a.local_flags + kGraphCntBase +
-                           (uint64_t)a.slot * kMaxGraphBlocks + blockIdx.x;
-        __shared__ uint64_t s_seq;
-        if (threadIdx.x == 0) {
-            s_seq = __hip_atomic_fetch_add(my_cnt, 1, __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT) +
-                    1;
-        }
-        __syncthreads();
-        seq          = s_seq;
-        par          = (seq & 1) * a.parity_stride;
-        stage_target = seq * (uint64_t)a.nblocks;
-        cap          = kSpinLimit;
-    } else {
-        seq          = a.seq;
-        par          = 0;
-        stage_target = a.stage_target;
-        cap          = spin_cap(a.spin_limit);
-    }
+    const FusedIter it = fused_iter<DEV_SEQ>(a);
+    const uint64_t  par = it.par;
     /* 1. stage src -> my scratch (all blocks, grid-stride, 16B packs; the
      * parity area of this iteration) */
     {
@@ -63,45 +40,10 @@ __device__ __forceinline__ void fused_body(const Args &a)
             ((T *)mysc)[i] = ((const T *)a.src)[i];
         }
     }
-    __threadfence_system();
-    __syncthreads();
-    /* 2. grid arrival: each block bumps the staging counter; block 0
-     * waits for all blocks, then signals every peer (incl. self) with seq.
-     * The staging counter (u64 index kStageCntBase + slot) is monotone and
-     * grows by nblocks per use -> target seq*nblocks. */
-    uint64_t *stage_cnt = a.local_flags + kStageCntBase + a.slot;
-    __shared__ int s_err;
-    if (threadIdx.x == 0) {
-        s_err = 0;
-        __hip_atomic_fetch_add(stage_cnt, 1, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (blockIdx.x == 0) {
-        if (threadIdx.x == 0 &&
-            !spin_until(stage_cnt, stage_target, cap, a.error_word)) {
-            s_err = 1;
-        }
-        __syncthreads();
-        if (!s_err && (int)threadIdx.x < a.nranks) {
-            sys_store(a.peer_flags[threadIdx.x] +
-                          (uint64_t)a.slot * kMaxRanks + a.rank,
-                      seq);
-        }
-    }
-    /* 3. all blocks wait for all ranks' arrivals (timeout: all threads
-     * leave together — never return while siblings sit at a barrier) */
-    if (!s_err && (int)threadIdx.x < a.nranks &&
-        !spin_until(a.local_flags + (uint64_t)a.slot * kMaxRanks +
-                        threadIdx.x,
-                    seq, cap, a.error_word)) {
-        s_err = 1;
-    }
-    __syncthreads();
-    if (s_err) {
+    /* 2.-3. publish, signal every peer, wait for all ranks */
+    if (!fused_handshake(a, it)) {
         return;
     }
-    __threadfence_system(); /* acquire: drop stale lines before peer reads */
     /* 4. reduce all peers' scratch (this iteration's parity) into dst.
      * Why parity is sufficient: a peer can start staging replay i+1 while
      * I still read its replay-i data (staging precedes the handshake),
@@ -110,29 +52,9 @@ __device__ __forceinline__ void fused_body(const Args &a)
      * MY i+1 launch — stream-ordered after my reduce of i finished. */
     reduce_range<T, OP, VEC>(a.dst, a.peer_scratch, par, a.nranks, a.count,
                              a.alpha);
-    /* 5. host-visible completion: the last arriving block publishes
-     * done_seq to the pinned word — the host polls plain memory
-     * instead of event record+query (see FusedArgs.done_host). dst
-     * stores are fenced before the arrival add; the release store
-     * makes them visible to the host with the flag. */
+    /* 5. host-visible completion */
     if constexpr (!DEV_SEQ) {
-        if (a.done_host) {
-            __threadfence_system();
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                uint64_t v = __hip_atomic_fetch_add(
-                                 a.local_flags + kFusedDoneBase + a.slot, 1,
-                                 __ATOMIC_ACQ_REL,
-                                 __HIP_MEMORY_SCOPE_AGENT) +
-                             1;
-                if (v == a.done_target) {
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    __hip_atomic_store(a.done_host, a.done_seq,
-                                       __ATOMIC_RELEASE,
-                                       __HIP_MEMORY_SCOPE_SYSTEM);
-                }
-            }
-        }
+        fused_publish_done(a);
     }
 }
 

@@ -21,7 +21,9 @@
  *
  * Algorithms here (v1): allreduce (fused small / staged-linear large),
  * allgather(v), reduce_scatter(v), bcast, reduce. Host-memory colls and
- * everything else fall back per the score map.
+ * everything else fall back per the score map. Opt-in: the fused kernel's
+ * protocol for small allgather / reduce_scatter / alltoall / bcast / reduce
+ * (FusedCollTask, fused_plan.h).
  */
 #include <atomic>
 #include <map>
@@ -36,6 +38,7 @@
 #include "../shm/slot_seg.h"
 #include "p2p_mbox.h"
 #include "ring_plan.h"
+#include "fused_plan.h"
 
 namespace ucc {
 namespace {
@@ -54,6 +57,8 @@ using ec_hip::kMaxRanks;
 static_assert(kRingMaxRings == ec_hip::kMaxRings &&
                   kRingMaxRanks == ec_hip::kMaxRanks,
               "ring_plan.h and ec_hip.h disagree");
+static_assert(kFusedMaxRanks == ec_hip::kMaxRanks,
+              "fused_plan.h and ec_hip.h disagree");
 
 /* v-coll count/displacement accessors honoring the 64-bit flags
  * (reference: ucc_coll_utils count conventions). */
@@ -105,6 +110,8 @@ struct Cdna4Cfg {
     bool     gated_rooted; /* gated_pipeline for full-team bcast/reduce  */
     bool     ring;       /* offer the multi-ring algorithms              */
     int      ring_nrings; /* rings to use, 0 = auto (ring_plan.h)        */
+    bool     fused_colls; /* fused one-kernel ag/rs/a2a/bcast/reduce       */
+    size_t   fused_colls_max; /* bound on the plan's scratch_bytes         */
 };
 
 class Cdna4Tl;
@@ -740,6 +747,247 @@ class FusedAllreduceTask final : public Cdna4Task {
   private:
     size_t bytes_ = 0;
     int    pslot_ = -1;
+};
+
+/* Fused single-kernel allgather / reduce_scatter / alltoall / bcast /
+ * reduce (small messages; opt-in, UCC_TL_CDNA4_FUSED_COLLS). The slot
+ * sequencing, the cumulative stage and completion counters and the timeout
+ * are FusedAllreduceTask's, on the same words, so the two compose on one
+ * slot sequence; what is staged and read comes from fused_plan.h. */
+class FusedCollTask final : public Cdna4Task {
+  public:
+    using Cdna4Task::Cdna4Task;
+
+    /* what the accept / decline decision and the plan need from the
+     * arguments; everything but inplace of REDUCE is equal on every rank */
+    struct Shape {
+        FusedColl      coll;
+        ucc_datatype_t dt;
+        uint64_t       block; /* bytes: per-rank block, or the vector */
+        bool           inplace;
+    };
+    static bool shape(const ucc_coll_args_t &a, uint32_t n, Shape *s)
+    {
+        const bool inplace = a.flags & UCC_COLL_ARGS_FLAG_IN_PLACE;
+        uint64_t   count;
+        switch (a.coll_type) {
+        case UCC_COLL_TYPE_ALLGATHER:
+            s->coll = FUSED_ALLGATHER;
+            s->dt   = a.dst.info.datatype;
+            count   = a.dst.info.count / n;
+            break;
+        case UCC_COLL_TYPE_ALLTOALL:
+            s->coll = FUSED_ALLTOALL;
+            s->dt   = a.dst.info.datatype;
+            count   = a.dst.info.count / n;
+            break;
+        case UCC_COLL_TYPE_REDUCE_SCATTER:
+            s->coll = FUSED_REDUCE_SCATTER;
+            s->dt   = a.dst.info.datatype;
+            count   = inplace ? a.dst.info.count / n : a.dst.info.count;
+            break;
+        case UCC_COLL_TYPE_BCAST:
+            s->coll = FUSED_BCAST;
+            s->dt   = a.src.info.datatype;
+            count   = a.src.info.count;
+            break;
+        case UCC_COLL_TYPE_REDUCE:
+            s->coll = FUSED_REDUCE;
+            s->dt   = a.src.info.datatype;
+            count   = a.src.info.count;
+            break;
+        default: return false;
+        }
+        if (!ucc_dt_is_predefined(s->dt)) {
+            return false;
+        }
+        s->block   = count * ucc_dt_size(s->dt);
+        s->inplace = inplace;
+        return true;
+    }
+
+    /* Rank-invariant by construction: counts, dtype, op, n, flags and knobs
+     * only, never a pointer (alignment is the kernel's business). A
+     * rank-local decline would put ranks on different algorithms. */
+    static bool supported(const ucc_coll_args_t &a, const Cdna4TlTeam *tt)
+    {
+        const uint32_t n = tt->team_->size;
+        Shape          s;
+        if (!shape(a, n, &s) || s.block == 0 || a.root >= n ||
+            (s.coll == FUSED_ALLTOALL && s.inplace)) {
+            return false;
+        }
+        if ((s.coll == FUSED_REDUCE_SCATTER || s.coll == FUSED_REDUCE) &&
+            !ec_hip::op_supported(s.dt, a.op)) {
+            return false;
+        }
+        size_t bound = tt->cfg_.fused_colls_max;
+        if (bound > tt->cfg_.chunk) {
+            bound = tt->cfg_.chunk; /* the parity area is one chunk */
+        }
+        return s.block <= bound &&
+               fused_plan_scratch_bytes(s.coll, (int)n, s.block) <= bound;
+    }
+
+    ucc_status_t post() override
+    {
+        begin_use();
+        status = UCC_INPROGRESS;
+        return progress();
+    }
+
+    ucc_status_t progress() override
+    {
+        if (phase_ == 0) {
+            if (!all_ge(0)) {
+                return UCC_INPROGRESS;
+            }
+            ec_hip::FusedCollArgs fa{};
+            FusedPlan             pl;
+            ucc_status_t          st = fill(&fa, &pl, slot_);
+            if (st != UCC_OK) {
+                return st;
+            }
+            fa.seq        = fseq_;
+            fa.spin_limit = tt_->spin_limit();
+            /* one block per 128 KiB of the larger of staged and read
+             * bytes */
+            const uint64_t big = pl.stage_bytes > pl.read_bytes
+                                     ? pl.stage_bytes
+                                     : pl.read_bytes;
+            const uint64_t blocks = (big + 128 * 1024 - 1) / (128 * 1024);
+            fa.nblocks = (int)(blocks < 1 ? 1 : blocks > 16 ? 16 : blocks);
+            if (tt_->stage_cum_.size() < tt_->cfg_.nslots) {
+                tt_->stage_cum_.assign(tt_->cfg_.nslots, 0);
+                tt_->done_cum_.assign(tt_->cfg_.nslots, 0);
+            }
+            tt_->stage_cum_[slot_] += (uint64_t)fa.nblocks;
+            fa.stage_target = tt_->stage_cum_[slot_];
+            tt_->done_cum_[slot_] += (uint64_t)fa.nblocks;
+            fa.done_target = tt_->done_cum_[slot_];
+            fa.done_seq    = fseq_;
+            fa.done_host   = tt_->done_host_ + slot_;
+            ucc_debug("cdna4 fused %s: host-sequenced kernel (k_fused_coll), "
+                      "%d blocks, %zu scratch bytes",
+                      coll_type_name(a_.coll_type), fa.nblocks,
+                      (size_t)pl.scratch_bytes);
+            st = ec_hip::fused_coll(fa, comp());
+            if (st != UCC_OK) {
+                return st;
+            }
+            phase_ = 1;
+        }
+        if (phase_ == 1) {
+            if (*tt_->err_host_ != 0) {
+                ucc_error("fused %s timed out waiting for peers",
+                          coll_type_name(a_.coll_type));
+                close_slot();
+                return UCC_ERR_TIMED_OUT;
+            }
+            if (__atomic_load_n(tt_->done_host_ + slot_,
+                                __ATOMIC_ACQUIRE) < fseq_) {
+                return UCC_INPROGRESS;
+            }
+            close_slot();
+            return UCC_OK;
+        }
+        return UCC_INPROGRESS;
+    }
+
+    /* Stream-triggered (and hipGraph-capturable) post, as
+     * FusedAllreduceTask::triggered_post: one kernel with a device-derived
+     * iteration number on a PK_FUSED persistent slot. */
+    ucc_status_t triggered_post(void *ee_stream) override
+    {
+        if (pslot_ < 0) {
+            pslot_ = tt_->alloc_pslot(Cdna4TlTeam::PK_FUSED);
+            if (pslot_ < 0) {
+                ucc_error("no free persistent slot (TL_CDNA4 "
+                          "PERSISTENT_SLOTS exhausted or pattern "
+                          "mismatch)");
+                return UCC_ERR_NO_RESOURCE;
+            }
+            me_ = tt_->team_->rank;
+            n_  = tt_->team_->size;
+        }
+        ec_hip::FusedCollArgs ga{};
+        FusedPlan             pl;
+        ucc_status_t          st = fill(&ga, &pl, (uint32_t)pslot_);
+        if (st != UCC_OK) {
+            return st;
+        }
+        ga.parity_stride = 2 * tt_->cfg_.chunk;
+        /* FIXED grid: per-block launch counters must advance uniformly
+         * across every request that ever reuses this slot */
+        ga.nblocks = 8;
+        ucc_debug("cdna4 fused %s: graph kernel (k_fused_coll_graph), "
+                  "%d blocks, %zu scratch bytes",
+                  coll_type_name(a_.coll_type), ga.nblocks,
+                  (size_t)pl.scratch_bytes);
+        st = ec_hip::fused_coll_graph(ga, (hipStream_t)ee_stream);
+        if (st != UCC_OK) {
+            return st;
+        }
+        status = UCC_OK;
+        return UCC_OK;
+    }
+
+    ~FusedCollTask() override
+    {
+        if (pslot_ >= 0) {
+            tt_->free_pslot(pslot_);
+        }
+    }
+
+  private:
+    /* the plan and everything of the kernel argument that does not depend
+     * on how the launch is sequenced */
+    ucc_status_t fill(ec_hip::FusedCollArgs *fa, FusedPlan *pl, uint32_t slot)
+    {
+        Shape s;
+        if (!shape(a_, n_, &s) ||
+            !fused_plan_init(pl, s.coll, (int)n_, (int)me_, (int)a_.root,
+                             s.block, ucc_dt_size(s.dt), s.inplace) ||
+            pl->scratch_bytes > tt_->cfg_.chunk) {
+            return UCC_ERR_NOT_SUPPORTED;
+        }
+        void *ubuf_dst = s.coll == FUSED_BCAST ? a_.src.info.buffer
+                                               : a_.dst.info.buffer;
+        fa->dst = ubuf_dst;
+        fa->src = pl->src_is_dst ? ubuf_dst : a_.src.info.buffer;
+        fa->my_scratch = tt_->area(me_, slot, 0, 0);
+        for (uint32_t r = 0; r < n_; r++) {
+            fa->peer_scratch[r] = tt_->area(r, slot, 0, 0);
+            fa->peer_flags[r]   = tt_->peers_[r].flags;
+        }
+        fa->local_flags = tt_->flags_;
+        fa->rank        = (int)me_;
+        fa->nranks      = (int)n_;
+        fa->slot        = (int)slot;
+        fa->error_word  = tt_->err_host_;
+        fa->n_cells     = pl->n_cells;
+        for (int k = 0; k < pl->n_cells; k++) {
+            fa->c_src_off[k] = pl->cell[k].src_off;
+            fa->c_sc_off[k]  = pl->cell[k].scratch_off;
+            fa->c_len[k]     = pl->cell[k].len;
+        }
+        fa->n_segs = pl->n_segs;
+        for (int k = 0; k < pl->n_segs; k++) {
+            fa->g_peer[k]    = pl->seg[k].peer;
+            fa->g_sc_off[k]  = pl->seg[k].scratch_off;
+            fa->g_dst_off[k] = pl->seg[k].dst_off;
+            fa->g_len[k]     = pl->seg[k].len;
+        }
+        fa->r_sc_off  = pl->red_scratch_off;
+        fa->r_dst_off = pl->red_dst_off;
+        fa->r_count   = pl->red_count;
+        fa->dt        = s.dt;
+        fa->op        = a_.op == UCC_OP_AVG ? (ucc_reduction_op_t)12 : a_.op;
+        fa->alpha     = a_.op == UCC_OP_AVG ? 1.0 / (double)n_ : 1.0;
+        return UCC_OK;
+    }
+
+    int pslot_ = -1;
 };
 
 /* Staged linear collectives: allreduce / allgather(v) / reduce_scatter(v) /
@@ -3471,6 +3719,22 @@ class Cdna4Tl final : public Tl {
                     "gather at the root, zero-copy for persistent and "
                     "large requests) instead of staged_linear; must be "
                     "the same on every rank");
+        cfg.declare("TL_CDNA4", "FUSED_COLLS", "0",
+                    "serve small full-team device allgather, "
+                    "reduce_scatter, alltoall, bcast and reduce with one "
+                    "fused kernel per rank (algorithm 'fused', score 100; "
+                    "stage, handshake, read over the peer mappings, "
+                    "hipGraph-replayable); must be the same on every rank");
+        cfg.declare("TL_CDNA4", "FUSED_COLLS_MAX", "8k",
+                    "max scratch bytes of one fused collective (the "
+                    "per-rank block of allgather, n blocks of "
+                    "reduce_scatter and alltoall, the vector of bcast and "
+                    "reduce, blocks rounded up to 16); capped at "
+                    "CHUNK_SIZE. Default: the largest size at which "
+                    "fused beat every other path of all five types, "
+                    "persistent zero-copy reduce_scatter included; "
+                    "one-shot requests gain up to 1m "
+                    "(profiles/fused_colls.md)");
         if (!cfg.get_bool("TL_CDNA4", "ENABLE", true) ||
             !mc::hip_available()) {
             return nullptr;
@@ -3532,6 +3796,9 @@ class Cdna4Tl final : public Tl {
         if (c.ring_nrings > kRingMaxRings) {
             c.ring_nrings = kRingMaxRings;
         }
+        c.fused_colls = cfg.get_bool("TL_CDNA4", "FUSED_COLLS", false);
+        c.fused_colls_max =
+            cfg.get_size("TL_CDNA4", "FUSED_COLLS_MAX", 8 * 1024);
         return new Cdna4TlTeam(tlc, team, c);
     }
 };
@@ -3670,6 +3937,43 @@ void Cdna4TlTeam::get_scores(Team *team, ScoreMap &map)
             return UCC_OK;
         };
         map.add(UCC_COLL_TYPE_BCAST, UCC_MEMORY_TYPE_CUDA, r);
+    }
+    if (cfg_.fused_colls) {
+        /* opt-in (UCC_TL_CDNA4_FUSED_COLLS): unset, the map is exactly the
+         * entries below. A declined request (over the bound, in-place
+         * alltoall, ...) falls through to them. */
+        ScoreRange r;
+        r.start    = 0;
+        r.end      = SIZE_MAX;
+        r.score    = 100;
+        r.tl_name  = "cdna4";
+        r.alg_name = "fused";
+        r.init     = [self](const ucc_coll_args_t &args, Team *t,
+                        Task **task) -> ucc_status_t {
+            if ((args.mask & UCC_COLL_ARGS_FIELD_ACTIVE_SET) ||
+                !FusedCollTask::supported(args, self)) {
+                return UCC_ERR_NOT_SUPPORTED;
+            }
+            /* spinning kernels of several ranks of one process can share
+             * a HW queue: see the fused allreduce below */
+            int same_proc = 0;
+            for (auto &p : t->procs) {
+                same_proc += (p.pid == t->ctx->proc.pid);
+            }
+            if (same_proc > 1) {
+                return UCC_ERR_NOT_SUPPORTED;
+            }
+            *task = new FusedCollTask(t->ctx, self, args);
+            return UCC_OK;
+        };
+        for (auto ct : {UCC_COLL_TYPE_ALLGATHER, UCC_COLL_TYPE_REDUCE_SCATTER,
+                        UCC_COLL_TYPE_ALLTOALL, UCC_COLL_TYPE_BCAST,
+                        UCC_COLL_TYPE_REDUCE}) {
+            for (auto mt :
+                 {UCC_MEMORY_TYPE_CUDA, UCC_MEMORY_TYPE_CUDA_MANAGED}) {
+                map.add(ct, mt, r);
+            }
+        }
     }
     add(UCC_COLL_TYPE_ALLREDUCE, 0, cfg_.fused_max, 100, "fused", true);
     if (Config::instance().get_bool("TL_CDNA4", "GATED", true)) {
