@@ -41,7 +41,8 @@ SHLIB  := $(BUILD)/libucc_amd.so
 PERFTEST := build/ucc_perftest
 INFO     := build/ucc_info
 NTESTS   := build/test_generic_dt build/test_obj_size build/test_mt \
-            build/test_p2p_mbox build/test_ring_plan build/test_fused_plan
+            build/test_p2p_mbox build/test_ring_plan build/test_fused_plan \
+            build/test_fused_plan_v
 
 all: $(MODULE) $(SHLIB) $(PERFTEST) $(INFO) $(NTESTS)
 
@@ -68,6 +69,10 @@ build/test_ring_plan: $(BUILD)/tests/test_ring_plan.o
 
 # host-only: the fused-collective plan header and nothing else of the library
 build/test_fused_plan: $(BUILD)/tests/test_fused_plan.o
+	$(HIPCC) $^ -o $@
+
+# host-only: the v-forms of the same header
+build/test_fused_plan_v: $(BUILD)/tests/test_fused_plan_v.o
 	$(HIPCC) $^ -o $@
 
 $(BUILD)/tools/%.o: tools/%.cc tools/shm_oob.h

@@ -165,6 +165,28 @@ struct FusedCollArgs {
 ucc_status_t fused_coll(const FusedCollArgs &a, hipStream_t stream);
 ucc_status_t fused_coll_graph(const FusedCollArgs &a, hipStream_t stream);
 
+/* Fused small-message alltoallv (k_fused_a2av, host-sequenced only). No rank
+ * can tell from its own send row and recv column whether every pair fits a
+ * scratch cell, so the ranks vote inside the kernel:
+ *   1. thread 0 of block 0 stores my vote, 2 * seq + fits_local, into the
+ *      16-byte header at my_scratch + 0; a rank that fits stages its cells
+ *      (c.n_cells, as fused_coll), a rank that does not stages nothing
+ *   2. the handshake of fused_coll, whatever the vote
+ *   3. every block reads the nranks headers: the verdict is "fits" iff every
+ *      vote is 2 * seq + 1
+ *   4. "fits": copy the c.n_segs segments; otherwise dst is not touched
+ *   5. the last block stores 2 * done_seq + verdict to *verdict_host
+ *      (host-pinned), then release-stores the completion word.
+ * c is a plan of fused_plan_init_v(FUSED_ALLTOALLV): cells and segments lie
+ * behind the header; r_count must be 0. error_word keeps its meaning
+ * (handshake timeout); the verdict never touches it. */
+struct FusedA2avArgs {
+    FusedCollArgs c;
+    int           fits_local;
+    uint64_t     *verdict_host;
+};
+ucc_status_t fused_a2av(const FusedA2avArgs &a, hipStream_t stream);
+
 bool dt_supported(ucc_datatype_t dt);
 bool op_supported(ucc_datatype_t dt, ucc_reduction_op_t op);
 

@@ -2,7 +2,9 @@
  * reduce_scatter, alltoall, bcast and reduce, host-sequenced (k_fused_coll)
  * and graph-capturable (k_fused_coll_graph). One body, two kernels; the
  * sequencing, handshake and completion steps are the fused allreduce's
- * (ec_device.h, "fused one-kernel protocol"). */
+ * (ec_device.h, "fused one-kernel protocol"). allgatherv and
+ * reduce_scatterv run the same kernels with another plan; alltoallv has the
+ * host-sequenced k_fused_a2av at the end of this file. */
 #include "ec_device.h"
 
 namespace ucc {
@@ -142,6 +144,83 @@ ucc_status_t fused_coll_graph(const FusedCollArgs &a_in, hipStream_t s)
     FusedCollArgs a = a_in;
     a.dt            = fold_complex(a.dt, a.op, &a.r_count);
     return dispatch<LaunchFusedRedGraph>(a.dt, a.op, a, s);
+}
+
+/* ------------------------------------------------------------ alltoallv */
+/* The fused alltoallv: the protocol above with a vote (FusedA2avArgs in
+ * ec_hip.h). The only waits are the bounded ones of fused_handshake.
+ *
+ * Why every block of every rank reaches the same verdict: a rank stores its
+ * vote before the fence and the arrival add of its block 0, block 0 signals
+ * the peers only after that, and a block reads the n headers only after it
+ * saw all n signals of this seq. A vote carries the seq, so a header left
+ * by an earlier use of the slot never reads as "fits". */
+__global__ void k_fused_a2av(FusedA2avArgs a)
+{
+    const FusedCollArgs &c  = a.c;
+    const FusedIter      it = fused_iter<false>(c);
+    uint8_t             *mysc = (uint8_t *)c.my_scratch;
+    /* 1. my vote, then my cells (none if I do not fit) */
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        sys_store((uint64_t *)mysc, 2 * it.seq + (a.fits_local ? 1 : 0));
+    }
+    if (a.fits_local) {
+        for (int k = 0; k < c.n_cells; k++) {
+            d_copy_bytes(mysc + c.c_sc_off[k],
+                         (const uint8_t *)c.src + c.c_src_off[k], c.c_len[k]);
+        }
+    }
+    /* 2. every rank takes part, whatever it voted */
+    if (!fused_handshake(c, it)) {
+        return;
+    }
+    /* 3. the verdict: n votes through LDS */
+    __shared__ int s_unfit;
+    if (threadIdx.x == 0) {
+        s_unfit = 0;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < c.nranks &&
+        sys_load((const uint64_t *)c.peer_scratch[threadIdx.x]) !=
+            2 * it.seq + 1) {
+        atomicOr(&s_unfit, 1);
+    }
+    __syncthreads();
+    const bool fits = s_unfit == 0;
+    /* 4. my segments, or nothing */
+    if (fits) {
+        for (int k = 0; k < c.n_segs; k++) {
+            d_copy_bytes((uint8_t *)c.dst + c.g_dst_off[k],
+                         (const uint8_t *)c.peer_scratch[c.g_peer[k]] +
+                             c.g_sc_off[k],
+                         c.g_len[k]);
+        }
+    }
+    /* 5. fused_publish_done with the verdict stored before the release */
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t v = __hip_atomic_fetch_add(
+                         c.local_flags + kFusedDoneBase + c.slot, 1,
+                         __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) +
+                     1;
+        if (v == c.done_target) {
+            sys_store(a.verdict_host, 2 * c.done_seq + (fits ? 1 : 0));
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __hip_atomic_store(c.done_host, c.done_seq, __ATOMIC_RELEASE,
+                               __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+ucc_status_t fused_a2av(const FusedA2avArgs &a, hipStream_t s)
+{
+    if (!fused_coll_args_ok(a.c, 1024) || a.c.r_count != 0 ||
+        !a.verdict_host || !a.c.done_host) {
+        return UCC_ERR_INVALID_PARAM;
+    }
+    hipLaunchKernelGGL(k_fused_a2av, dim3(a.c.nblocks), dim3(256), 0, s, a);
+    return launch_status();
 }
 
 } // namespace ec_hip

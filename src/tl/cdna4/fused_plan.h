@@ -34,7 +34,11 @@
  *   reduce in place, root    source = dst
  *   bcast                    always in place (one buffer)
  *   alltoall in place        declined
- * dst_off counts from the user dst. */
+ * dst_off counts from the user dst.
+ *
+ * The ragged forms (allgatherv, reduce_scatterv, alltoallv) have an
+ * initialiser of their own, fused_plan_init_v, described at its definition;
+ * tests/native/test_fused_plan_v.cc runs it for all ranks. */
 #ifndef UCC_AMD_FUSED_PLAN_H_
 #define UCC_AMD_FUSED_PLAN_H_
 
@@ -46,7 +50,10 @@ namespace ucc {
 constexpr int kFusedMaxRanks = 8;
 
 enum FusedColl { FUSED_ALLGATHER = 0, FUSED_REDUCE_SCATTER = 1,
-                 FUSED_ALLTOALL = 2, FUSED_BCAST = 3, FUSED_REDUCE = 4 };
+                 FUSED_ALLTOALL = 2, FUSED_BCAST = 3, FUSED_REDUCE = 4,
+                 /* v-forms: fused_plan_init_v below */
+                 FUSED_ALLGATHERV = 5, FUSED_REDUCE_SCATTERV = 6,
+                 FUSED_ALLTOALLV = 7 };
 
 struct FusedCell {
     uint64_t src_off = 0, scratch_off = 0, len = 0; /* bytes */
@@ -71,6 +78,9 @@ struct FusedPlan {
     uint64_t  scratch_bytes = 0;
     uint64_t  stage_bytes = 0; /* sum of the cells                        */
     uint64_t  read_bytes = 0;  /* bytes read over peer pointers           */
+    /* alltoallv only */
+    uint64_t  cell_bytes = 0;  /* the fixed cell size                     */
+    bool      fits_local = true; /* my vote: all my send lengths <= cell  */
 };
 
 static inline uint64_t fused_plan_stride(uint64_t block_bytes)
@@ -178,6 +188,214 @@ static inline bool fused_plan_init(FusedPlan *p, FusedColl coll, int n,
         p->read_bytes += p->seg[s].len;
     }
     p->read_bytes += p->red_count * elem_size * (uint64_t)n;
+    return true;
+}
+
+/* ------------------------------------------------------------- v-forms
+ * allgatherv, reduce_scatterv and alltoallv: byte counts and byte
+ * displacements per rank instead of one block size.
+ *
+ *   allgatherv      counts / displs = dst.info_v of every rank (the same
+ *                   array everywhere). Cell 0 = my block; segment r =
+ *                   counts[r] bytes of peer r's cell 0 -> dst + displs[r].
+ *                   In place: source = dst + displs[me].
+ *                   scratch_bytes = stride(max counts).
+ *   reduce_scatterv counts = dst.info_v.counts of every rank. Cell d = my
+ *                   contribution to rank d at the running sum of
+ *                   stride(counts[k]), k < d; the source is read packed in
+ *                   rank order and displacements are ignored (StagedTask's
+ *                   rule). Reduce segment = counts[me] / elem elements at my
+ *                   cell. In place: source = the whole packed dst, result at
+ *                   the packed offset of me. scratch_bytes = the sum of the
+ *                   strides. A rank whose count is 0 stages its cells and
+ *                   shakes hands, but has no reduce segment.
+ *   alltoallv       counts / displs = my send row, rcounts / rdispls = my
+ *                   recv column: NOT equal on every rank. A 16-byte header
+ *                   (the rank's vote) at scratch offset 0, then n cells of
+ *                   the fixed size `cell` (fused_plan_a2av_cell: knobs and n
+ *                   only, equal on every rank). Cell d at 16 + d * cell = my
+ *                   block for rank d; segment r = rcounts[r] bytes of peer
+ *                   r's cell me -> dst + rdispls[r]. fits_local = every one
+ *                   of my send lengths <= cell; a rank that does not fit
+ *                   stages nothing. Whether the segments run is decided in
+ *                   the kernel from all n votes (k_fused_a2av): a rank never
+ *                   knows from its own row and column that all pairs fit.
+ * Zero-length blocks make no cell and no segment. */
+
+/* largest alltoallv pair: what is left of `bound` after the header, split n
+ * ways, rounded down to 16. 0: no room. */
+static inline uint64_t fused_plan_a2av_cell(uint64_t bound, int n)
+{
+    if (n < 1 || bound < 16) {
+        return 0;
+    }
+    return ((bound - 16) / (uint64_t)n) & ~(uint64_t)15;
+}
+
+/* scratch_bytes of a v-plan from quantities equal on every rank: the counts
+ * array of allgatherv / reduce_scatterv, `cell` alone for alltoallv (counts
+ * is not read). UINT64_MAX: not expressible. */
+static inline uint64_t fused_plan_scratch_bytes_v(FusedColl coll, int n,
+                                                  const uint64_t *counts,
+                                                  uint64_t cell)
+{
+    if (n < 2 || n > kFusedMaxRanks) {
+        return UINT64_MAX;
+    }
+    uint64_t total = 0;
+    switch (coll) {
+    case FUSED_ALLTOALLV: return 16 + (uint64_t)n * cell;
+    case FUSED_ALLGATHERV:
+        for (int r = 0; r < n; r++) {
+            if (counts[r] > (UINT64_MAX >> 8)) {
+                return UINT64_MAX;
+            }
+            const uint64_t s = fused_plan_stride(counts[r]);
+            total            = s > total ? s : total;
+        }
+        return total;
+    case FUSED_REDUCE_SCATTERV:
+        for (int r = 0; r < n; r++) {
+            if (counts[r] > (UINT64_MAX >> 8)) {
+                return UINT64_MAX;
+            }
+            total += fused_plan_stride(counts[r]);
+        }
+        return total;
+    default: return UINT64_MAX;
+    }
+}
+
+/* false: not expressible (rank count, a count that is no multiple of the
+ * element size, all counts zero, in-place alltoallv, cell < 16). rcounts,
+ * rdispls and cell matter for alltoallv only; elem_size for reduce_scatterv
+ * only (alltoallv lengths are bytes of each side's own datatype). */
+static inline bool fused_plan_init_v(FusedPlan *p, FusedColl coll, int n,
+                                     int rank, const uint64_t *counts,
+                                     const uint64_t *displs,
+                                     const uint64_t *rcounts,
+                                     const uint64_t *rdispls, uint64_t cell,
+                                     size_t elem_size, bool inplace)
+{
+    if (n < 2 || n > kFusedMaxRanks || rank < 0 || rank >= n ||
+        elem_size == 0 || !counts) {
+        return false;
+    }
+    *p      = FusedPlan{};
+    p->coll = coll;
+    p->n    = n;
+    p->rank = rank;
+    const uint64_t sb = fused_plan_scratch_bytes_v(coll, n, counts, cell);
+    if (sb == UINT64_MAX) {
+        return false;
+    }
+    p->scratch_bytes = sb;
+    uint64_t any     = 0;
+    switch (coll) {
+    case FUSED_ALLGATHERV:
+        if (!displs) {
+            return false;
+        }
+        p->src_is_dst = inplace;
+        if (counts[rank]) {
+            p->n_cells         = 1;
+            p->cell[0].src_off = inplace ? displs[rank] : 0;
+            p->cell[0].len     = counts[rank];
+        }
+        for (int r = 0; r < n; r++) {
+            any |= counts[r];
+            if (!counts[r]) {
+                continue;
+            }
+            FusedSeg &s = p->seg[p->n_segs++];
+            s.peer      = r;
+            s.dst_off   = displs[r];
+            s.len       = counts[r];
+        }
+        break;
+    case FUSED_REDUCE_SCATTERV: {
+        p->src_is_dst   = inplace;
+        uint64_t packed = 0, sc = 0;
+        for (int d = 0; d < n; d++) {
+            if (counts[d] % elem_size != 0) {
+                return false;
+            }
+            any |= counts[d];
+            if (d == rank) {
+                p->red_scratch_off = sc;
+                p->red_dst_off     = inplace ? packed : 0;
+                p->red_count       = counts[d] / elem_size;
+            }
+            if (counts[d]) {
+                FusedCell &c  = p->cell[p->n_cells++];
+                c.src_off     = packed;
+                c.scratch_off = sc;
+                c.len         = counts[d];
+            }
+            packed += counts[d];
+            sc += fused_plan_stride(counts[d]);
+        }
+        break;
+    }
+    case FUSED_ALLTOALLV:
+        if (inplace || cell < 16 || cell % 16 != 0 || !displs || !rcounts ||
+            !rdispls) {
+            return false;
+        }
+        p->cell_bytes = cell;
+        p->fits_local = true;
+        for (int d = 0; d < n; d++) {
+            if (counts[d] > cell) {
+                p->fits_local = false;
+            }
+        }
+        for (int d = 0; p->fits_local && d < n; d++) {
+            if (!counts[d]) {
+                continue;
+            }
+            FusedCell &c  = p->cell[p->n_cells++];
+            c.src_off     = displs[d];
+            c.scratch_off = 16 + (uint64_t)d * cell;
+            c.len         = counts[d];
+        }
+        for (int r = 0; r < n; r++) {
+            /* a length over the cell is never read: the verdict of such a
+             * request is "does not fit" on every rank */
+            if (!rcounts[r] || rcounts[r] > cell) {
+                continue;
+            }
+            FusedSeg &s   = p->seg[p->n_segs++];
+            s.peer        = r;
+            s.scratch_off = 16 + (uint64_t)rank * cell;
+            s.dst_off     = rdispls[r];
+            s.len         = rcounts[r];
+        }
+        any = 1; /* the counts never decide */
+        break;
+    default: return false;
+    }
+    if (!any) {
+        return false;
+    }
+    for (int c = 0; c < p->n_cells; c++) {
+        p->stage_bytes += p->cell[c].len;
+    }
+    for (int s = 0; s < p->n_segs; s++) {
+        p->read_bytes += p->seg[s].len;
+    }
+    p->read_bytes += p->red_count * elem_size * (uint64_t)n;
+    return true;
+}
+
+/* the alltoallv verdict, as k_fused_a2av takes it after the handshake: the
+ * segments run only if every rank voted fits_local */
+static inline bool fused_plan_a2av_verdict(const bool *votes, int n)
+{
+    for (int r = 0; r < n; r++) {
+        if (!votes[r]) {
+            return false;
+        }
+    }
     return true;
 }
 

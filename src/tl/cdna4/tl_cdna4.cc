@@ -23,7 +23,8 @@
  * allgather(v), reduce_scatter(v), bcast, reduce. Host-memory colls and
  * everything else fall back per the score map. Opt-in: the fused kernel's
  * protocol for small allgather / reduce_scatter / alltoall / bcast / reduce
- * (FusedCollTask, fused_plan.h).
+ * (FusedCollTask, fused_plan.h), for allgatherv / reduce_scatterv, and for
+ * alltoallv with a vote inside the kernel (FusedA2avTask).
  */
 #include <atomic>
 #include <map>
@@ -110,7 +111,8 @@ struct Cdna4Cfg {
     bool     gated_rooted; /* gated_pipeline for full-team bcast/reduce  */
     bool     ring;       /* offer the multi-ring algorithms              */
     int      ring_nrings; /* rings to use, 0 = auto (ring_plan.h)        */
-    bool     fused_colls; /* fused one-kernel ag/rs/a2a/bcast/reduce       */
+    bool     fused_colls; /* fused one-kernel ag/rs/a2a/bcast/reduce and
+                             their v-forms                                */
     size_t   fused_colls_max; /* bound on the plan's scratch_bytes         */
 };
 
@@ -299,10 +301,12 @@ class Cdna4TlTeam final : public TlTeam {
             HIPCHK(hipMalloc((void **)&flags_, ec_hip::kFlagsBytes));
         }
         HIPCHK(hipMemset(flags_, 0, ec_hip::kFlagsBytes));
-        HIPCHK(hipHostMalloc((void **)&err_host_, 256,
+        HIPCHK(hipHostMalloc((void **)&err_host_, 512,
                              hipHostMallocDefault));
-        memset((void *)err_host_, 0, 256);
+        memset((void *)err_host_, 0, 512);
         done_host_  = err_host_ + 8;  /* [8..15]: per-slot fused flags */
+        /* [32..39]: per-slot verdict of the fused alltoallv's vote */
+        verdict_host_ = err_host_ + 32;
         gdone_host_ = err_host_ + 16; /* [16..23]: per-slot gated flags */
         p2p_done_host_ = err_host_ + 24; /* [24]: p2p pull launch seq   */
         /* p2p pull arrival counter: an allocation of its own, clear of
@@ -440,6 +444,17 @@ class Cdna4TlTeam final : public TlTeam {
 
     void get_scores(Team *team, ScoreMap &map) override;
 
+    /* What the score map's gated_pipeline and staged_linear / fused
+     * allreduce entries build, with their checks. init_unfused: the task a
+     * request gets with UCC_TL_CDNA4_FUSED_COLLS unset (gated where that
+     * entry exists and accepts, else staged), and its algorithm name. */
+    ucc_status_t init_gated(const ucc_coll_args_t &args, Team *t,
+                            Task **task);
+    ucc_status_t init_staged(const ucc_coll_args_t &args, Team *t,
+                             bool fused, Task **task);
+    ucc_status_t init_unfused(const ucc_coll_args_t &args, Team *t,
+                              Task **task, const char **alg);
+
     uint8_t *area(uint32_t rank, uint32_t slot, uint32_t parity, int which)
     {
         return peers_[rank].scratch +
@@ -508,6 +523,7 @@ class Cdna4TlTeam final : public TlTeam {
     uint64_t   *flags_ = nullptr;  /* device fine-grained               */
     uint64_t   *err_host_  = nullptr; /* host-pinned, device-writable   */
     uint64_t   *done_host_ = nullptr; /* per-slot fused completion flags */
+    uint64_t   *verdict_host_ = nullptr; /* per-slot fused alltoallv votes */
     uint64_t   *gdone_host_ = nullptr; /* per-slot gated completion flags */
     std::vector<uint64_t> done_cum_;  /* cumulative completion arrivals  */
     std::vector<uint64_t> gdone_seq_; /* per-slot gated completion seqs  */
@@ -749,7 +765,41 @@ class FusedAllreduceTask final : public Cdna4Task {
     int    pslot_ = -1;
 };
 
-/* Fused single-kernel allgather / reduce_scatter / alltoall / bcast /
+/* what the team, the slot and a plan decide of a fused kernel's argument:
+ * scratch and flag pointers, cells, segments, the reduce segment */
+static void fused_args_from_plan(Cdna4TlTeam *tt, uint32_t me, uint32_t n,
+                                 uint32_t slot, const FusedPlan &pl,
+                                 ec_hip::FusedCollArgs *fa)
+{
+    fa->my_scratch = tt->area(me, slot, 0, 0);
+    for (uint32_t r = 0; r < n; r++) {
+        fa->peer_scratch[r] = tt->area(r, slot, 0, 0);
+        fa->peer_flags[r]   = tt->peers_[r].flags;
+    }
+    fa->local_flags = tt->flags_;
+    fa->rank        = (int)me;
+    fa->nranks      = (int)n;
+    fa->slot        = (int)slot;
+    fa->error_word  = tt->err_host_;
+    fa->n_cells     = pl.n_cells;
+    for (int k = 0; k < pl.n_cells; k++) {
+        fa->c_src_off[k] = pl.cell[k].src_off;
+        fa->c_sc_off[k]  = pl.cell[k].scratch_off;
+        fa->c_len[k]     = pl.cell[k].len;
+    }
+    fa->n_segs = pl.n_segs;
+    for (int k = 0; k < pl.n_segs; k++) {
+        fa->g_peer[k]    = pl.seg[k].peer;
+        fa->g_sc_off[k]  = pl.seg[k].scratch_off;
+        fa->g_dst_off[k] = pl.seg[k].dst_off;
+        fa->g_len[k]     = pl.seg[k].len;
+    }
+    fa->r_sc_off  = pl.red_scratch_off;
+    fa->r_dst_off = pl.red_dst_off;
+    fa->r_count   = pl.red_count;
+}
+
+/* Fused single-kernel allgather(v) / reduce_scatter(v) / alltoall / bcast /
  * reduce (small messages; opt-in, UCC_TL_CDNA4_FUSED_COLLS). The slot
  * sequencing, the cumulative stage and completion counters and the timeout
  * are FusedAllreduceTask's, on the same words, so the two compose on one
@@ -763,14 +813,42 @@ class FusedCollTask final : public Cdna4Task {
     struct Shape {
         FusedColl      coll;
         ucc_datatype_t dt;
-        uint64_t       block; /* bytes: per-rank block, or the vector */
+        uint64_t       block; /* bytes: per-rank block, or the vector;
+                                 v-forms: the largest block             */
         bool           inplace;
+        /* v-forms: bytes per rank, dst.info_v of every rank (allgatherv;
+         * reduce_scatterv reads its source packed, dsp stays 0) */
+        uint64_t       cnt[kFusedMaxRanks], dsp[kFusedMaxRanks];
     };
+    static bool is_v(FusedColl c)
+    {
+        return c == FUSED_ALLGATHERV || c == FUSED_REDUCE_SCATTERV;
+    }
     static bool shape(const ucc_coll_args_t &a, uint32_t n, Shape *s)
     {
         const bool inplace = a.flags & UCC_COLL_ARGS_FLAG_IN_PLACE;
         uint64_t   count;
         switch (a.coll_type) {
+        case UCC_COLL_TYPE_ALLGATHERV:
+        case UCC_COLL_TYPE_REDUCE_SCATTERV: {
+            const bool agv = a.coll_type == UCC_COLL_TYPE_ALLGATHERV;
+            s->coll = agv ? FUSED_ALLGATHERV : FUSED_REDUCE_SCATTERV;
+            s->dt   = a.dst.info_v.datatype;
+            if (n > (uint32_t)kFusedMaxRanks || !ucc_dt_is_predefined(s->dt)) {
+                return false;
+            }
+            const uint64_t es = ucc_dt_size(s->dt);
+            s->block          = 0;
+            s->inplace        = inplace;
+            for (uint32_t r = 0; r < n; r++) {
+                s->cnt[r] = coll_count_at(a, a.dst.info_v.counts, r) * es;
+                s->dsp[r] =
+                    agv ? coll_disp_at(a, a.dst.info_v.displacements, r) * es
+                        : 0;
+                s->block = s->cnt[r] > s->block ? s->cnt[r] : s->block;
+            }
+            return true;
+        }
         case UCC_COLL_TYPE_ALLGATHER:
             s->coll = FUSED_ALLGATHER;
             s->dt   = a.dst.info.datatype;
@@ -813,17 +891,25 @@ class FusedCollTask final : public Cdna4Task {
     {
         const uint32_t n = tt->team_->size;
         Shape          s;
-        if (!shape(a, n, &s) || s.block == 0 || a.root >= n ||
+        /* s.block == 0 for a v-form: every count is zero */
+        if (!shape(a, n, &s) || s.block == 0 ||
+            (!is_v(s.coll) && a.root >= n) ||
             (s.coll == FUSED_ALLTOALL && s.inplace)) {
             return false;
         }
-        if ((s.coll == FUSED_REDUCE_SCATTER || s.coll == FUSED_REDUCE) &&
+        if ((s.coll == FUSED_REDUCE_SCATTER || s.coll == FUSED_REDUCE ||
+             s.coll == FUSED_REDUCE_SCATTERV) &&
             !ec_hip::op_supported(s.dt, a.op)) {
             return false;
         }
         size_t bound = tt->cfg_.fused_colls_max;
         if (bound > tt->cfg_.chunk) {
             bound = tt->cfg_.chunk; /* the parity area is one chunk */
+        }
+        if (is_v(s.coll)) {
+            /* dst.info_v.counts is the same array on every rank */
+            return fused_plan_scratch_bytes_v(s.coll, (int)n, s.cnt, 0) <=
+                   bound;
         }
         return s.block <= bound &&
                fused_plan_scratch_bytes(s.coll, (int)n, s.block) <= bound;
@@ -946,41 +1032,22 @@ class FusedCollTask final : public Cdna4Task {
     {
         Shape s;
         if (!shape(a_, n_, &s) ||
-            !fused_plan_init(pl, s.coll, (int)n_, (int)me_, (int)a_.root,
-                             s.block, ucc_dt_size(s.dt), s.inplace) ||
+            !(is_v(s.coll)
+                  ? fused_plan_init_v(pl, s.coll, (int)n_, (int)me_, s.cnt,
+                                      s.dsp, nullptr, nullptr, 0,
+                                      ucc_dt_size(s.dt), s.inplace)
+                  : fused_plan_init(pl, s.coll, (int)n_, (int)me_,
+                                    (int)a_.root, s.block, ucc_dt_size(s.dt),
+                                    s.inplace)) ||
             pl->scratch_bytes > tt_->cfg_.chunk) {
             return UCC_ERR_NOT_SUPPORTED;
         }
         void *ubuf_dst = s.coll == FUSED_BCAST ? a_.src.info.buffer
+                         : is_v(s.coll)        ? a_.dst.info_v.buffer
                                                : a_.dst.info.buffer;
         fa->dst = ubuf_dst;
         fa->src = pl->src_is_dst ? ubuf_dst : a_.src.info.buffer;
-        fa->my_scratch = tt_->area(me_, slot, 0, 0);
-        for (uint32_t r = 0; r < n_; r++) {
-            fa->peer_scratch[r] = tt_->area(r, slot, 0, 0);
-            fa->peer_flags[r]   = tt_->peers_[r].flags;
-        }
-        fa->local_flags = tt_->flags_;
-        fa->rank        = (int)me_;
-        fa->nranks      = (int)n_;
-        fa->slot        = (int)slot;
-        fa->error_word  = tt_->err_host_;
-        fa->n_cells     = pl->n_cells;
-        for (int k = 0; k < pl->n_cells; k++) {
-            fa->c_src_off[k] = pl->cell[k].src_off;
-            fa->c_sc_off[k]  = pl->cell[k].scratch_off;
-            fa->c_len[k]     = pl->cell[k].len;
-        }
-        fa->n_segs = pl->n_segs;
-        for (int k = 0; k < pl->n_segs; k++) {
-            fa->g_peer[k]    = pl->seg[k].peer;
-            fa->g_sc_off[k]  = pl->seg[k].scratch_off;
-            fa->g_dst_off[k] = pl->seg[k].dst_off;
-            fa->g_len[k]     = pl->seg[k].len;
-        }
-        fa->r_sc_off  = pl->red_scratch_off;
-        fa->r_dst_off = pl->red_dst_off;
-        fa->r_count   = pl->red_count;
+        fused_args_from_plan(tt_, me_, n_, slot, *pl, fa);
         fa->dt        = s.dt;
         fa->op        = a_.op == UCC_OP_AVG ? (ucc_reduction_op_t)12 : a_.op;
         fa->alpha     = a_.op == UCC_OP_AVG ? 1.0 / (double)n_ : 1.0;
@@ -988,6 +1055,174 @@ class FusedCollTask final : public Cdna4Task {
     }
 
     int pslot_ = -1;
+};
+
+/* Fused single-kernel alltoallv (small pairs; opt-in with the same knob). A
+ * rank knows its send row and its recv column only, so the accept / decline
+ * decision cannot look at the counts: every request that passes supported()
+ * launches k_fused_a2av, the ranks vote inside the kernel whether every pair
+ * fits a cell (fused_plan.h, ec_hip.h), and all of them read the same
+ * verdict. "Fits": the kernel has done the exchange. "Does not fit": no dst
+ * byte was touched, the slot is closed, and the request is served, on a
+ * fresh slot use, by the task it would have got with the knob unset
+ * (Cdna4TlTeam::init_unfused). Slot sequencing, cumulative counters and the
+ * timeout are FusedCollTask's. A captured graph cannot fall back, so a
+ * triggered post goes to the inner task directly. */
+class FusedA2avTask final : public Cdna4Task {
+  public:
+    using Cdna4Task::Cdna4Task;
+
+    static uint64_t cell_bytes(const Cdna4TlTeam *tt)
+    {
+        size_t bound = tt->cfg_.fused_colls_max;
+        if (bound > tt->cfg_.chunk) {
+            bound = tt->cfg_.chunk;
+        }
+        return fused_plan_a2av_cell(bound, (int)tt->team_->size);
+    }
+
+    /* knobs, n, flags and datatypes only: never the counts */
+    static bool supported(const ucc_coll_args_t &a, const Cdna4TlTeam *tt)
+    {
+        return a.coll_type == UCC_COLL_TYPE_ALLTOALLV &&
+               tt->team_->size <= (uint32_t)kFusedMaxRanks &&
+               cell_bytes(tt) >= 16 &&
+               !(a.flags & UCC_COLL_ARGS_FLAG_IN_PLACE) &&
+               ucc_dt_is_predefined(a.src.info_v.datatype) &&
+               ucc_dt_is_predefined(a.dst.info_v.datatype);
+    }
+
+    ucc_status_t post() override
+    {
+        begin_use();
+        status = UCC_INPROGRESS;
+        return progress();
+    }
+
+    ucc_status_t progress() override
+    {
+        if (phase_ == 0) {
+            if (!all_ge(0)) {
+                return UCC_INPROGRESS;
+            }
+            ec_hip::FusedA2avArgs fa{};
+            FusedPlan             pl;
+            const uint64_t        cell = cell_bytes(tt_);
+            const uint64_t sdt = ucc_dt_size(a_.src.info_v.datatype);
+            const uint64_t rdt = ucc_dt_size(a_.dst.info_v.datatype);
+            uint64_t       sc[kFusedMaxRanks], sd[kFusedMaxRanks],
+                rc[kFusedMaxRanks], rd[kFusedMaxRanks];
+            for (uint32_t r = 0; r < n_; r++) {
+                sc[r] = coll_count_at(a_, a_.src.info_v.counts, r) * sdt;
+                sd[r] =
+                    coll_disp_at(a_, a_.src.info_v.displacements, r) * sdt;
+                rc[r] = coll_count_at(a_, a_.dst.info_v.counts, r) * rdt;
+                rd[r] =
+                    coll_disp_at(a_, a_.dst.info_v.displacements, r) * rdt;
+            }
+            if (!fused_plan_init_v(&pl, FUSED_ALLTOALLV, (int)n_, (int)me_,
+                                   sc, sd, rc, rd, cell, 1, false) ||
+                pl.scratch_bytes > tt_->cfg_.chunk) {
+                return UCC_ERR_NOT_SUPPORTED;
+            }
+            fa.c.dst = a_.dst.info_v.buffer;
+            fa.c.src = a_.src.info_v.buffer;
+            fused_args_from_plan(tt_, me_, n_, slot_, pl, &fa.c);
+            fa.c.seq        = fseq_;
+            fa.c.spin_limit = tt_->spin_limit();
+            fa.fits_local   = pl.fits_local ? 1 : 0;
+            /* one block per 128 KiB of the larger of staged and read
+             * bytes; the stage counter is rank-local, so grids may differ
+             * between ranks */
+            const uint64_t big = pl.stage_bytes > pl.read_bytes
+                                     ? pl.stage_bytes
+                                     : pl.read_bytes;
+            const uint64_t blocks = (big + 128 * 1024 - 1) / (128 * 1024);
+            fa.c.nblocks =
+                (int)(blocks < 1 ? 1 : blocks > 16 ? 16 : blocks);
+            if (tt_->stage_cum_.size() < tt_->cfg_.nslots) {
+                tt_->stage_cum_.assign(tt_->cfg_.nslots, 0);
+                tt_->done_cum_.assign(tt_->cfg_.nslots, 0);
+            }
+            tt_->stage_cum_[slot_] += (uint64_t)fa.c.nblocks;
+            fa.c.stage_target = tt_->stage_cum_[slot_];
+            tt_->done_cum_[slot_] += (uint64_t)fa.c.nblocks;
+            fa.c.done_target = tt_->done_cum_[slot_];
+            fa.c.done_seq    = fseq_;
+            fa.c.done_host   = tt_->done_host_ + slot_;
+            fa.verdict_host  = tt_->verdict_host_ + slot_;
+            cell_            = (size_t)cell;
+            ucc_debug("cdna4 fused alltoallv: host-sequenced kernel "
+                      "(k_fused_a2av), %d blocks, cell %zu bytes",
+                      fa.c.nblocks, cell_);
+            ucc_status_t st = ec_hip::fused_a2av(fa, comp());
+            if (st != UCC_OK) {
+                return st;
+            }
+            phase_ = 1;
+        }
+        if (phase_ == 1) {
+            if (*tt_->err_host_ != 0) {
+                ucc_error("fused alltoallv timed out waiting for peers");
+                close_slot();
+                return UCC_ERR_TIMED_OUT;
+            }
+            if (__atomic_load_n(tt_->done_host_ + slot_,
+                                __ATOMIC_ACQUIRE) < fseq_) {
+                return UCC_INPROGRESS;
+            }
+            /* stored before the completion word's release */
+            const uint64_t verdict = __atomic_load_n(
+                tt_->verdict_host_ + slot_, __ATOMIC_RELAXED);
+            close_slot();
+            if (verdict == 2 * fseq_ + 1) {
+                return UCC_OK;
+            }
+            /* every rank read the same verdict: all fall back together */
+            ucc_status_t st = make_inner();
+            if (st != UCC_OK) {
+                return st;
+            }
+            ucc_debug("cdna4 fused alltoallv: a pair exceeds the %zu-byte "
+                      "cell, served by %s",
+                      cell_, inner_alg_);
+            phase_ = 2;
+            return inner_->post();
+        }
+        if (phase_ == 2) {
+            return inner_->progress();
+        }
+        return UCC_INPROGRESS;
+    }
+
+    ucc_status_t triggered_post(void *ee_stream) override
+    {
+        ucc_status_t st = make_inner();
+        if (st != UCC_OK) {
+            return st;
+        }
+        st = inner_->triggered_post(ee_stream);
+        if (st == UCC_OK) {
+            status = inner_->status.load();
+        }
+        return st;
+    }
+
+    ~FusedA2avTask() override { delete inner_; }
+
+  private:
+    /* built on first need, kept across re-posts of a persistent request */
+    ucc_status_t make_inner()
+    {
+        if (inner_) {
+            return UCC_OK;
+        }
+        return tt_->init_unfused(a_, tt_->team_, &inner_, &inner_alg_);
+    }
+
+    Task       *inner_     = nullptr;
+    const char *inner_alg_ = "";
+    size_t      cell_      = 0;
 };
 
 /* Staged linear collectives: allreduce / allgather(v) / reduce_scatter(v) /
@@ -3720,16 +3955,23 @@ class Cdna4Tl final : public Tl {
                     "large requests) instead of staged_linear; must be "
                     "the same on every rank");
         cfg.declare("TL_CDNA4", "FUSED_COLLS", "0",
-                    "serve small full-team device allgather, "
-                    "reduce_scatter, alltoall, bcast and reduce with one "
-                    "fused kernel per rank (algorithm 'fused', score 100; "
-                    "stage, handshake, read over the peer mappings, "
-                    "hipGraph-replayable); must be the same on every rank");
+                    "serve small full-team device allgather, allgatherv, "
+                    "reduce_scatter, reduce_scatterv, alltoall, alltoallv, "
+                    "bcast and reduce with one fused kernel per rank "
+                    "(algorithm 'fused', score 100; stage, handshake, read "
+                    "over the peer mappings, hipGraph-replayable but for "
+                    "alltoallv, whose ranks vote in the kernel whether "
+                    "every pair fits and else fall back together); must be "
+                    "the same on every rank");
         cfg.declare("TL_CDNA4", "FUSED_COLLS_MAX", "8k",
                     "max scratch bytes of one fused collective (the "
                     "per-rank block of allgather, n blocks of "
                     "reduce_scatter and alltoall, the vector of bcast and "
-                    "reduce, blocks rounded up to 16); capped at "
+                    "reduce, blocks rounded up to 16; allgatherv: the "
+                    "largest block; reduce_scatterv: the sum of the "
+                    "blocks; alltoallv: a 16-byte header and n cells, so "
+                    "the largest fused pair is (MAX - 16) / n rounded down "
+                    "to 16); capped at "
                     "CHUNK_SIZE. Default: the largest size at which "
                     "fused beat every other path of all five types, "
                     "persistent zero-copy reduce_scatter included; "
@@ -3807,6 +4049,98 @@ static Cdna4Tl g_cdna4_tl;
 
 Tl *Cdna4TlContext::iface() { return &g_cdna4_tl; }
 
+ucc_status_t Cdna4TlTeam::init_gated(const ucc_coll_args_t &args, Team *t,
+                                     Task **task)
+{
+    if (args.mask & UCC_COLL_ARGS_FIELD_ACTIVE_SET) {
+        return UCC_ERR_NOT_SUPPORTED; /* active_set_p2p only */
+    }
+    if (args.coll_type == UCC_COLL_TYPE_ALLREDUCE ||
+        args.coll_type == UCC_COLL_TYPE_REDUCE_SCATTER ||
+        args.coll_type == UCC_COLL_TYPE_REDUCE_SCATTERV) {
+        ucc_datatype_t gdt = args.coll_type == UCC_COLL_TYPE_REDUCE_SCATTERV
+                                 ? args.dst.info_v.datatype
+                                 : args.dst.info.datatype;
+        if (!ec_hip::op_supported(gdt, args.op)) {
+            return UCC_ERR_NOT_SUPPORTED;
+        }
+    }
+    if (args.coll_type == UCC_COLL_TYPE_REDUCE &&
+        !ec_hip::op_supported(args.src.info.datatype, args.op)) {
+        return UCC_ERR_NOT_SUPPORTED;
+    }
+    /* in-process multi-rank jigs can serialize spinning kernels on one HW
+     * queue: host-gated staged path is the safe fallback there (same
+     * reasoning as the fused kernel). */
+    int same_proc = 0;
+    for (auto &p : t->procs) {
+        same_proc += (p.pid == t->ctx->proc.pid);
+    }
+    if (same_proc > 1) {
+        return UCC_ERR_NOT_SUPPORTED;
+    }
+    *task = new GatedCollTask(t->ctx, this, args);
+    return UCC_OK;
+}
+
+ucc_status_t Cdna4TlTeam::init_staged(const ucc_coll_args_t &args, Team *t,
+                                      bool fused, Task **task)
+{
+    /* subset colls never take the team-wide slot sequence: non-members
+     * post nothing (active_set_p2p serves bcast) */
+    if (args.mask & UCC_COLL_ARGS_FIELD_ACTIVE_SET) {
+        return UCC_ERR_NOT_SUPPORTED;
+    }
+    /* reductions need a supported dtype x op on device */
+    if (args.coll_type == UCC_COLL_TYPE_ALLREDUCE ||
+        args.coll_type == UCC_COLL_TYPE_REDUCE ||
+        args.coll_type == UCC_COLL_TYPE_REDUCE_SCATTER ||
+        args.coll_type == UCC_COLL_TYPE_REDUCE_SCATTERV) {
+        ucc_datatype_t dt = args.coll_type == UCC_COLL_TYPE_REDUCE_SCATTERV
+                                ? args.dst.info_v.datatype
+                                : args.dst.info.datatype;
+        if (args.coll_type == UCC_COLL_TYPE_REDUCE) {
+            dt = args.src.info.datatype;
+        }
+        if (!ec_hip::op_supported(dt, args.op)) {
+            return UCC_ERR_NOT_SUPPORTED;
+        }
+    }
+    if (fused) {
+        /* The fused kernel spin-waits for every peer's kernel. With
+         * several ranks of one process on one GPU (the in-process jig)
+         * their streams can share a HW queue and event barrier packets
+         * serialize the dispatches -> deadlock. One process per GPU
+         * (production) is safe; same-process multi-rank falls back to the
+         * host-gated staged path. */
+        int same_proc = 0;
+        for (auto &p : t->procs) {
+            same_proc += (p.pid == t->ctx->proc.pid);
+        }
+        if (same_proc > 1) {
+            return UCC_ERR_NOT_SUPPORTED;
+        }
+        *task = new FusedAllreduceTask(t->ctx, this, args);
+    } else {
+        *task = new StagedTask(t->ctx, this, args);
+    }
+    return UCC_OK;
+}
+
+ucc_status_t Cdna4TlTeam::init_unfused(const ucc_coll_args_t &args, Team *t,
+                                       Task **task, const char **alg)
+{
+    /* get_scores() below registers gated_pipeline for the v-forms exactly
+     * when GATED is set */
+    if (Config::instance().get_bool("TL_CDNA4", "GATED", true) &&
+        init_gated(args, t, task) == UCC_OK) {
+        *alg = "gated_pipeline";
+        return UCC_OK;
+    }
+    *alg = "staged_linear";
+    return init_staged(args, t, false, task);
+}
+
 void Cdna4TlTeam::get_scores(Team *team, ScoreMap &map)
 {
     (void)team;
@@ -3821,36 +4155,7 @@ void Cdna4TlTeam::get_scores(Team *team, ScoreMap &map)
         r.alg_name = "gated_pipeline";
         r.init     = [self](const ucc_coll_args_t &args, Team *t,
                         Task **task) -> ucc_status_t {
-            if (args.mask & UCC_COLL_ARGS_FIELD_ACTIVE_SET) {
-                return UCC_ERR_NOT_SUPPORTED; /* active_set_p2p only */
-            }
-            if (args.coll_type == UCC_COLL_TYPE_ALLREDUCE ||
-                args.coll_type == UCC_COLL_TYPE_REDUCE_SCATTER ||
-                args.coll_type == UCC_COLL_TYPE_REDUCE_SCATTERV) {
-                ucc_datatype_t gdt =
-                    args.coll_type == UCC_COLL_TYPE_REDUCE_SCATTERV
-                        ? args.dst.info_v.datatype
-                        : args.dst.info.datatype;
-                if (!ec_hip::op_supported(gdt, args.op)) {
-                    return UCC_ERR_NOT_SUPPORTED;
-                }
-            }
-            if (args.coll_type == UCC_COLL_TYPE_REDUCE &&
-                !ec_hip::op_supported(args.src.info.datatype, args.op)) {
-                return UCC_ERR_NOT_SUPPORTED;
-            }
-            /* in-process multi-rank jigs can serialize spinning kernels
-             * on one HW queue: host-gated staged path is the safe
-             * fallback there (same reasoning as the fused kernel). */
-            int same_proc = 0;
-            for (auto &p : t->procs) {
-                same_proc += (p.pid == t->ctx->proc.pid);
-            }
-            if (same_proc > 1) {
-                return UCC_ERR_NOT_SUPPORTED;
-            }
-            *task = new GatedCollTask(t->ctx, self, args);
-            return UCC_OK;
+            return self->init_gated(args, t, task);
         };
         for (auto mt : {UCC_MEMORY_TYPE_CUDA, UCC_MEMORY_TYPE_CUDA_MANAGED}) {
             map.add(ct, mt, r);
@@ -3866,47 +4171,7 @@ void Cdna4TlTeam::get_scores(Team *team, ScoreMap &map)
         r.alg_name = alg;
         r.init     = [self, fused](const ucc_coll_args_t &args, Team *t,
                                Task **task) -> ucc_status_t {
-            /* subset colls never take the team-wide slot sequence:
-             * non-members post nothing (active_set_p2p serves bcast) */
-            if (args.mask & UCC_COLL_ARGS_FIELD_ACTIVE_SET) {
-                return UCC_ERR_NOT_SUPPORTED;
-            }
-            /* reductions need a supported dtype x op on device */
-            if (args.coll_type == UCC_COLL_TYPE_ALLREDUCE ||
-                args.coll_type == UCC_COLL_TYPE_REDUCE ||
-                args.coll_type == UCC_COLL_TYPE_REDUCE_SCATTER ||
-                args.coll_type == UCC_COLL_TYPE_REDUCE_SCATTERV) {
-                ucc_datatype_t dt =
-                    args.coll_type == UCC_COLL_TYPE_REDUCE_SCATTERV
-                        ? args.dst.info_v.datatype
-                        : args.dst.info.datatype;
-                if (args.coll_type == UCC_COLL_TYPE_REDUCE) {
-                    dt = args.src.info.datatype;
-                }
-                if (!ec_hip::op_supported(dt, args.op)) {
-                    return UCC_ERR_NOT_SUPPORTED;
-                }
-            }
-            if (fused) {
-                /* The fused kernel spin-waits for every peer's kernel.
-                 * With several ranks of one process on one GPU (the
-                 * in-process jig) their streams can share a HW queue and
-                 * event barrier packets serialize the dispatches ->
-                 * deadlock. One process per GPU (production) is safe;
-                 * same-process multi-rank falls back to the host-gated
-                 * staged path. */
-                int same_proc = 0;
-                for (auto &p : t->procs) {
-                    same_proc += (p.pid == t->ctx->proc.pid);
-                }
-                if (same_proc > 1) {
-                    return UCC_ERR_NOT_SUPPORTED;
-                }
-                *task = new FusedAllreduceTask(t->ctx, self, args);
-            } else {
-                *task = new StagedTask(t->ctx, self, args);
-            }
-            return UCC_OK;
+            return self->init_staged(args, t, fused, task);
         };
         for (auto mt : {UCC_MEMORY_TYPE_CUDA, UCC_MEMORY_TYPE_CUDA_MANAGED}) {
             map.add(ct, mt, r);
@@ -3950,8 +4215,10 @@ void Cdna4TlTeam::get_scores(Team *team, ScoreMap &map)
         r.alg_name = "fused";
         r.init     = [self](const ucc_coll_args_t &args, Team *t,
                         Task **task) -> ucc_status_t {
+            const bool a2av = args.coll_type == UCC_COLL_TYPE_ALLTOALLV;
             if ((args.mask & UCC_COLL_ARGS_FIELD_ACTIVE_SET) ||
-                !FusedCollTask::supported(args, self)) {
+                !(a2av ? FusedA2avTask::supported(args, self)
+                       : FusedCollTask::supported(args, self))) {
                 return UCC_ERR_NOT_SUPPORTED;
             }
             /* spinning kernels of several ranks of one process can share
@@ -3963,12 +4230,18 @@ void Cdna4TlTeam::get_scores(Team *team, ScoreMap &map)
             if (same_proc > 1) {
                 return UCC_ERR_NOT_SUPPORTED;
             }
-            *task = new FusedCollTask(t->ctx, self, args);
+            if (a2av) {
+                *task = new FusedA2avTask(t->ctx, self, args);
+            } else {
+                *task = new FusedCollTask(t->ctx, self, args);
+            }
             return UCC_OK;
         };
         for (auto ct : {UCC_COLL_TYPE_ALLGATHER, UCC_COLL_TYPE_REDUCE_SCATTER,
                         UCC_COLL_TYPE_ALLTOALL, UCC_COLL_TYPE_BCAST,
-                        UCC_COLL_TYPE_REDUCE}) {
+                        UCC_COLL_TYPE_REDUCE, UCC_COLL_TYPE_ALLGATHERV,
+                        UCC_COLL_TYPE_REDUCE_SCATTERV,
+                        UCC_COLL_TYPE_ALLTOALLV}) {
             for (auto mt :
                  {UCC_MEMORY_TYPE_CUDA, UCC_MEMORY_TYPE_CUDA_MANAGED}) {
                 map.add(ct, mt, r);

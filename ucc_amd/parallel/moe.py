@@ -3,7 +3,16 @@
 The SURVEY §2.9 EP workload: tokens routed to experts on other ranks
 with skewed per-peer counts — a thin, correct dispatch/combine pair on
 the library's alltoallv (tl/cdna4 staged per-peer cells on device,
-shm/tcp on host)."""
+shm/tcp on host).
+
+Every dispatch and combine is a one-shot request: the counts change each
+step, so it cannot be persistent. On device tensors, with
+UCC_TL_CDNA4_FUSED_COLLS=1, tl/cdna4 serves it with one fused kernel per
+rank while every (sender, receiver) pair is at most
+(UCC_TL_CDNA4_FUSED_COLLS_MAX - 16) / world bytes, rounded down to 16: set
+the bound to about world x the largest expected pair. The ranks vote on
+that inside the kernel; a step with a larger pair is still right, it runs
+as without the knob after one extra kernel (docs/USER_GUIDE.md)."""
 
 import torch
 
