@@ -42,7 +42,7 @@ PERFTEST := build/ucc_perftest
 INFO     := build/ucc_info
 NTESTS   := build/test_generic_dt build/test_obj_size build/test_mt \
             build/test_p2p_mbox build/test_ring_plan build/test_fused_plan \
-            build/test_fused_plan_v
+            build/test_fused_plan_v build/test_zc_policy
 
 all: $(MODULE) $(SHLIB) $(PERFTEST) $(INFO) $(NTESTS)
 
@@ -73,6 +73,10 @@ build/test_fused_plan: $(BUILD)/tests/test_fused_plan.o
 
 # host-only: the v-forms of the same header
 build/test_fused_plan_v: $(BUILD)/tests/test_fused_plan_v.o
+	$(HIPCC) $^ -o $@
+
+# host-only: the grid / cache-policy rule header and nothing else
+build/test_zc_policy: $(BUILD)/tests/test_zc_policy.o
 	$(HIPCC) $^ -o $@
 
 $(BUILD)/tools/%.o: tools/%.cc tools/shm_oob.h
@@ -110,7 +114,8 @@ check: all
 	python3 -m pytest tests/ -x -q -m "not gpu"
 
 # Compiled resource usage of the fused zero-copy allreduce: no scratch,
-# flagship at 3 waves/SIMD, depth 4 at >= 2 (tools/check_zc_isa.py). A
+# flagship (plain and streamed) at 3 waves/SIMD, depth 4 at >= 2
+# (tools/check_zc_isa.py). A
 # device-only compile of the gated kernel unit; run it after any change to
 # zc_data_phase or a compiler update.
 check-isa:
@@ -171,9 +176,15 @@ build/asan_fused_plan: tests/native/test_fused_plan.cc src/tl/cdna4/fused_plan.h
 	$(HIPCC) -x c++ -std=c++17 -O1 -g -fsanitize=address,undefined \
 	    -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< -o $@
 
+build/asan_zc_policy: tests/native/test_zc_policy.cc src/tl/cdna4/zc_policy.h
+	$(HIPCC) -x c++ -std=c++17 -O1 -g -fsanitize=address,undefined \
+	    -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< -o $@
+
 .PHONY: asan
 asan: build/asan_generic_dt build/asan_obj_size build/asan_perftest \
-      build/asan_p2p_mbox build/asan_ring_plan build/asan_fused_plan
+      build/asan_p2p_mbox build/asan_ring_plan build/asan_fused_plan \
+      build/asan_zc_policy
+	ASAN_OPTIONS=detect_leaks=1 ./build/asan_zc_policy
 	ASAN_OPTIONS=detect_leaks=1 ./build/asan_p2p_mbox
 	ASAN_OPTIONS=detect_leaks=1 ./build/asan_ring_plan
 	ASAN_OPTIONS=detect_leaks=1 ./build/asan_fused_plan

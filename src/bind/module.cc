@@ -629,7 +629,7 @@ PYBIND11_MODULE(_core, m)
         "ec_zc_data",
         [](std::vector<uintptr_t> srcs, std::vector<uintptr_t> dsts,
            uint64_t sl_b, uint64_t sl_e, int dt, int op, int zc_write,
-           double alpha, int blocks, int threads, int reps) {
+           double alpha, int blocks, int threads, int reps, int stream) {
             const size_t n = srcs.size();
             if (n < 2 || n > (size_t)ucc::ec_hip::kMaxRanks ||
                 dsts.size() != (zc_write ? n : (size_t)1) || sl_e < sl_b ||
@@ -665,6 +665,11 @@ PYBIND11_MODULE(_core, m)
             a.alpha    = alpha;
             a.zc_write = zc_write ? 1 : 0;
             a.nblocks  = blocks;
+            a.zc_stream = stream ? 1 : 0;
+            if (a.zc_stream && !ucc::ec_hip::zc_has_stream((int)n)) {
+                /* before any stream or event exists */
+                check(UCC_ERR_NOT_SUPPORTED, "zc_data");
+            }
             hipStream_t st = nullptr;
             hipEvent_t  e0 = nullptr, e1 = nullptr;
             if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) !=
@@ -704,7 +709,7 @@ PYBIND11_MODULE(_core, m)
         py::arg("srcs"), py::arg("dsts"), py::arg("sl_b"), py::arg("sl_e"),
         py::arg("dt"), py::arg("op"), py::arg("zc_write"),
         py::arg("alpha"), py::arg("blocks"), py::arg("threads") = 256,
-        py::arg("reps") = 1);
+        py::arg("reps") = 1, py::arg("stream") = 0);
     /* the same for the bcast data phase (k_bcast_data): src is the root's
      * buffer base (the kernel adds sl_b), dsts are already offset by the
      * slice start. One dst: the zc_write = 0 form (my_out). Several: the

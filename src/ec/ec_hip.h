@@ -288,6 +288,10 @@ struct GatedArgs {
                                0 = kGatedBlocks default) */
     int         pull_wait;  /* 1 = poll peers' counters remotely instead
                                of local mirrors (debug fallback) */
+    int         zc_stream;  /* zc_allreduce / zc_data, read by the
+                               launcher only: 1 = the streamed (non-
+                               temporal) data phase where one is
+                               instantiated, see zc_has_stream() */
     /* host-pinned completion (set ONLY on the final kernel of a
      * host-posted collective): the last arriving block release-stores
      * done_seq after its signal push — host polls plain memory instead
@@ -321,8 +325,16 @@ ucc_status_t zc_allreduce(const GatedArgs &a, hipStream_t s);
  * peer_out[0..nranks) (zc_write = 1) or my_out (zc_write = 0); uses
  * sl_b, sl_e, nranks, dt, op, alpha and nblocks and nothing else of `a`.
  * threads: 64, 128 or 256 per block, 0 = what zc_allreduce would use.
- * Measurement probe and kernel unit-test hook. */
+ * Measurement probe and kernel unit-test hook. Unlike zc_allreduce, which
+ * quietly runs plain, zc_data with zc_stream set and no streamed
+ * instantiation for this rank count returns UCC_ERR_NOT_SUPPORTED. */
 ucc_status_t zc_data(const GatedArgs &a, hipStream_t s, int threads = 0);
+/* Whether zc_allreduce honours GatedArgs.zc_stream for this rank count:
+ * the streamed data phase (non-temporal batch loads of the peers' src and
+ * batch stores to the dsts) is instantiated at depth 4 only, i.e. 2 ranks
+ * at the default depth, the one case measured
+ * (profiles/zc_edges_stream.md). */
+bool zc_has_stream(int nranks);
 /* The batching depth U (4, 2 or 1) that zc_allreduce and zc_data run at
  * for this rank count, UCC_EC_REDUCE_DEPTH included. The host needs it
  * to size the grid: how many blocks of k_zc_allreduce a CU holds depends

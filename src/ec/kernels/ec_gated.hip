@@ -420,8 +420,38 @@ template <int U> struct ZcPeers {
     static constexpr int value = kMaxRanks / U > 0 ? kMaxRanks / U : 1;
 };
 
+/* 16-byte pack moves of the batches, by cache policy. NT: non-temporal
+ * (streaming) — a message that does not fit the Infinity Cache gains
+ * nothing from allocating there, and src is read and dst written exactly
+ * once per post. Pack is a struct, and the non-temporal builtins take
+ * scalar and vector types only, hence the bit casts. An nt store is an
+ * ordinary store to the memory model: the block's release at exit covers
+ * it like any other. */
+typedef uint32_t zc_u32x4 __attribute__((ext_vector_type(4)));
+template <bool NT, typename P>
+__device__ __forceinline__ P zc_ld(const P *p)
+{
+    static_assert(sizeof(P) == sizeof(zc_u32x4), "16-byte packs");
+    if constexpr (NT) {
+        return __builtin_bit_cast(
+            P, __builtin_nontemporal_load((const zc_u32x4 *)p));
+    } else {
+        return *p;
+    }
+}
+template <bool NT, typename P>
+__device__ __forceinline__ void zc_st(P *p, const P &v)
+{
+    if constexpr (NT) {
+        __builtin_nontemporal_store(__builtin_bit_cast(zc_u32x4, v),
+                                    (zc_u32x4 *)p);
+    } else {
+        *p = v;
+    }
+}
+
 /* issue one batch's U x n peer loads (no consumer in between) */
-template <typename P, int U, int NR>
+template <typename P, int U, int NR, bool NT>
 __device__ __forceinline__ void
 zc_batch_load(P (&x)[U][NR], const GatedArgs &a, int n, uint64_t i,
               uint64_t str)
@@ -433,7 +463,7 @@ zc_batch_load(P (&x)[U][NR], const GatedArgs &a, int n, uint64_t i,
                 (const P *)((const uint8_t *)a.peer_in[s] + a.sl_b);
 #pragma unroll
             for (int u = 0; u < U; u++) {
-                x[u][s] = src[i + (uint64_t)u * str];
+                x[u][s] = zc_ld<NT>(src + i + (uint64_t)u * str);
             }
         }
     }
@@ -441,7 +471,7 @@ zc_batch_load(P (&x)[U][NR], const GatedArgs &a, int n, uint64_t i,
 
 /* convert, reduce ranks 0..n-1 in order, scale, store one loaded batch:
  * the arithmetic of k_staged_reduce's batched loop, element for element */
-template <typename T, int OP, int VEC, int U, int NR, typename P>
+template <typename T, int OP, int VEC, int U, int NR, bool NT, typename P>
 __device__ __forceinline__ void
 zc_batch_reduce_store(const P (&x)[U][NR], const GatedArgs &a, P *out,
                       int n, uint64_t i, uint64_t str)
@@ -472,7 +502,8 @@ zc_batch_reduce_store(const P (&x)[U][NR], const GatedArgs &a, P *out,
             if (s < n) {
 #pragma unroll
                 for (int u = 0; u < U; u++) {
-                    ((P *)a.peer_out[s])[i + (uint64_t)u * str] = o[u];
+                    zc_st<NT>((P *)a.peer_out[s] + i + (uint64_t)u * str,
+                              o[u]);
                 }
             }
         }
@@ -485,7 +516,8 @@ zc_batch_reduce_store(const P (&x)[U][NR], const GatedArgs &a, P *out,
          * loop. */
 #pragma unroll
         for (int u = 0; u < U; u++) {
-            (NR > 2 ? out : (P *)a.my_out)[i + (uint64_t)u * str] = o[u];
+            zc_st<NT>((NR > 2 ? out : (P *)a.my_out) + i + (uint64_t)u * str,
+                      o[u]);
         }
     }
 }
@@ -496,7 +528,7 @@ zc_batch_reduce_store(const P (&x)[U][NR], const GatedArgs &a, P *out,
  * rank's src. No flag is read or written here, so k_zc_data below can
  * time it without a peer process (docs/GATED_PIPELINE.md "Data phase
  * and its probe"). */
-template <typename T, int OP, int VEC, int U>
+template <typename T, int OP, int VEC, int U, bool NT>
 __device__ __forceinline__ void zc_data_phase(const GatedArgs &a)
 {
     using A          = typename Cvt<T>::A;
@@ -535,26 +567,26 @@ __device__ __forceinline__ void zc_data_phase(const GatedArgs &a)
              * no branch around a load (see the note on n above): it
              * runs while batches i, i+bs and i+2bs all exist, and on
              * exit xa again holds batch i. */
-            zc_batch_load<P, U, NR>(xa, a, n, i, str);
+            zc_batch_load<P, U, NR, NT>(xa, a, n, i, str);
             while (i + 2 * bs + tail < nv) {
-                zc_batch_load<P, U, NR>(xb, a, n, i + bs, str);
-                zc_batch_reduce_store<T, OP, VEC, U, NR, P>(xa, a, out, n,
+                zc_batch_load<P, U, NR, NT>(xb, a, n, i + bs, str);
+                zc_batch_reduce_store<T, OP, VEC, U, NR, NT, P>(xa, a, out, n,
                                                             i, str);
-                zc_batch_load<P, U, NR>(xa, a, n, i + 2 * bs, str);
-                zc_batch_reduce_store<T, OP, VEC, U, NR, P>(xb, a, out, n,
+                zc_batch_load<P, U, NR, NT>(xa, a, n, i + 2 * bs, str);
+                zc_batch_reduce_store<T, OP, VEC, U, NR, NT, P>(xb, a, out, n,
                                                             i + bs, str);
                 i += 2 * bs;
             }
             /* epilogue: one or two full batches left */
             if (i + bs + tail < nv) {
-                zc_batch_load<P, U, NR>(xb, a, n, i + bs, str);
-                zc_batch_reduce_store<T, OP, VEC, U, NR, P>(xa, a, out, n,
+                zc_batch_load<P, U, NR, NT>(xb, a, n, i + bs, str);
+                zc_batch_reduce_store<T, OP, VEC, U, NR, NT, P>(xa, a, out, n,
                                                             i, str);
-                zc_batch_reduce_store<T, OP, VEC, U, NR, P>(xb, a, out, n,
+                zc_batch_reduce_store<T, OP, VEC, U, NR, NT, P>(xb, a, out, n,
                                                             i + bs, str);
                 i += 2 * bs;
             } else {
-                zc_batch_reduce_store<T, OP, VEC, U, NR, P>(xa, a, out, n,
+                zc_batch_reduce_store<T, OP, VEC, U, NR, NT, P>(xa, a, out, n,
                                                             i, str);
                 i += bs;
             }
@@ -623,23 +655,31 @@ __device__ __forceinline__ void zc_data_phase(const GatedArgs &a)
  * rank's dst. zc_write = 0: reduce_scatter, my slice goes to my_out only
  * and phase 2 is neither waited on nor signalled. See
  * docs/GATED_PIPELINE.md "Fused zero-copy allreduce". */
-template <typename T, int OP, int VEC, int U>
+template <typename T, int OP, int VEC, int U, bool NT>
 __global__ void __launch_bounds__(256) k_zc_allreduce(const GatedArgs a)
 {
     /* entry: block 0 is this rank's stage launch — area-reuse waits
      * (already satisfied in steady state), then "my stream reached this
      * post" on phase 0 (+1, so this one increment is the last arriver
-     * and pushes the mirrors) */
+     * and pushes the mirrors). Thread 0 alone, no block-wide fence: the
+     * block has stored nothing that the signal would publish. What the
+     * signal promises is that src is final, and src was written before
+     * the post (the API's contract) by work that ended at a kernel or
+     * copy boundary, which writes it back; the acq_rel add of
+     * gated_arrive is itself a release. zc_wait2 ended in a barrier, so
+     * the whole block is past its reuse wait. */
     if (blockIdx.x == 0) {
         if (!zc_wait2(a, 1, a.t_sw_reduce, 2, a.t_sw_gather)) {
             return;
         }
-        gated_signal(a, 0, a.t_sig_stage, /*pub_done=*/false);
+        if (threadIdx.x == 0) {
+            gated_arrive(a, 0, a.t_sig_stage);
+        }
     }
     if (!zc_wait2(a, 0, a.t_stage, 2, a.t_prev_gather)) {
         return;
     }
-    zc_data_phase<T, OP, VEC, U>(a);
+    zc_data_phase<T, OP, VEC, U, NT>(a);
     /* exit: every block counts on phase 1; the last arriver pushed the
      * mirrors and stays on as this rank's gather launch: wait for the
      * TEAM's reduces (every peer has written my dst and stopped reading
@@ -647,24 +687,34 @@ __global__ void __launch_bounds__(256) k_zc_allreduce(const GatedArgs a)
     if (!gated_signal_last(a, 1, a.t_sig_reduce)) {
         return;
     }
-    if (!gated_wait(a, 1, a.t_gather_wait)) {
+    /* one acquire by wave 0 and a barrier, as at entry (a 0 target is
+     * not waited on); on spin timeout all threads leave together */
+    if (!zc_wait2(a, 1, a.t_gather_wait, 2, 0)) {
         return;
     }
-    if (a.zc_write) {
-        gated_signal(a, 2, a.t_sig_gather, /*pub_done=*/true);
-    } else if (a.done_host && threadIdx.x == 0) {
-        __hip_atomic_store(a.done_host, a.done_seq, __ATOMIC_RELEASE,
-                           __HIP_MEMORY_SCOPE_SYSTEM);
+    /* One lane from here: the block has stored nothing since its phase-1
+     * arrive, so there is nothing for a block-wide fence to write back.
+     * Thread 0 is in the wave that acquired above, so its release add
+     * (phase 2) and its release store (done_host) stay ordered behind
+     * that acquire, and with it behind every peer's phase-1 release,
+     * i.e. behind their writes to my dst. */
+    if (threadIdx.x == 0) {
+        const bool last =
+            a.zc_write ? gated_arrive(a, 2, a.t_sig_gather) : true;
+        if (last && a.done_host) {
+            __hip_atomic_store(a.done_host, a.done_seq, __ATOMIC_RELEASE,
+                               __HIP_MEMORY_SCOPE_SYSTEM);
+        }
     }
 }
 
 /* The data phase alone, for measurement and unit tests: no flags, no
  * waits, no signals, so it runs without a peer process and hardware
  * counters can be collected on it. */
-template <typename T, int OP, int VEC, int U>
+template <typename T, int OP, int VEC, int U, bool NT>
 __global__ void __launch_bounds__(256) k_zc_data(const GatedArgs a)
 {
-    zc_data_phase<T, OP, VEC, U>(a);
+    zc_data_phase<T, OP, VEC, U, NT>(a);
 }
 
 /* ------------------------------------- rooted collectives: bcast phase */
@@ -923,13 +973,27 @@ static int zc_threads()
     return reduce_knobs().threads == 128 ? 128 : 256;
 }
 
+/* The streamed (NT) data phase exists at depth 4 only: 2 ranks at the
+ * default depth, the one case measured (profiles/zc_edges_stream.md). */
+bool zc_has_stream(int nranks)
+{
+    return nranks >= 2 && nranks <= kMaxRanks && zc_depth(nranks) == 4;
+}
+
 template <typename T, int OP> struct LaunchZcAllreduce {
     static ucc_status_t run(const GatedArgs &a, hipStream_t s)
     {
-        return launch_by_depth<4>(zc_depth(a.nranks), [&](auto u) {
+        if (a.zc_stream && zc_has_stream(a.nranks)) {
             hipLaunchKernelGGL(
-                (k_zc_allreduce<T, OP, VecOf<T>::value, decltype(u)::value>),
+                (k_zc_allreduce<T, OP, VecOf<T>::value, 4, true>),
                 dim3(gated_grid(a)), dim3(zc_threads()), 0, s, a);
+            return launch_status();
+        }
+        return launch_by_depth<4>(zc_depth(a.nranks), [&](auto u) {
+            hipLaunchKernelGGL((k_zc_allreduce<T, OP, VecOf<T>::value,
+                                               decltype(u)::value, false>),
+                               dim3(gated_grid(a)), dim3(zc_threads()), 0,
+                               s, a);
         });
     }
 };
@@ -941,10 +1005,17 @@ struct ZcDataLaunch {
 template <typename T, int OP> struct LaunchZcData {
     static ucc_status_t run(const ZcDataLaunch &l, hipStream_t s)
     {
+        if (l.a.zc_stream) { /* zc_data checked zc_has_stream */
+            hipLaunchKernelGGL((k_zc_data<T, OP, VecOf<T>::value, 4, true>),
+                               dim3(gated_grid(l.a)), dim3(l.threads), 0, s,
+                               l.a);
+            return launch_status();
+        }
         return launch_by_depth<4>(zc_depth(l.a.nranks), [&](auto u) {
-            hipLaunchKernelGGL(
-                (k_zc_data<T, OP, VecOf<T>::value, decltype(u)::value>),
-                dim3(gated_grid(l.a)), dim3(l.threads), 0, s, l.a);
+            hipLaunchKernelGGL((k_zc_data<T, OP, VecOf<T>::value,
+                                          decltype(u)::value, false>),
+                               dim3(gated_grid(l.a)), dim3(l.threads), 0, s,
+                               l.a);
         });
     }
 };
@@ -964,6 +1035,9 @@ ucc_status_t zc_data(const GatedArgs &a, hipStream_t s, int threads)
         (threads != 0 && threads != 64 && threads != 128 &&
          threads != 256)) {
         return UCC_ERR_INVALID_PARAM;
+    }
+    if (a.zc_stream && !zc_has_stream(a.nranks)) {
+        return UCC_ERR_NOT_SUPPORTED; /* no streamed instantiation */
     }
     const ZcDataLaunch l{a, threads ? threads : zc_threads()};
     return dispatch<LaunchZcData>(fold_complex(a.dt, a.op, nullptr), a.op,

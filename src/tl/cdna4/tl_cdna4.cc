@@ -40,6 +40,7 @@
 #include "p2p_mbox.h"
 #include "ring_plan.h"
 #include "fused_plan.h"
+#include "zc_policy.h"
 
 namespace ucc {
 namespace {
@@ -55,6 +56,8 @@ static inline void hip_warn_on_err(hipError_t e, const char *what)
 #define HIPWARN(expr) hip_warn_on_err((expr), #expr)
 
 using ec_hip::kMaxRanks;
+static_assert(tl_cdna4::kZcBlocksDefault == ec_hip::kGatedBlocks,
+              "zc_policy.h carries the default gated grid");
 static_assert(kRingMaxRings == ec_hip::kMaxRings &&
                   kRingMaxRanks == ec_hip::kMaxRanks,
               "ring_plan.h and ec_hip.h disagree");
@@ -103,6 +106,7 @@ struct Cdna4Cfg {
     size_t   chunk;     /* staging fragment bytes                     */
     size_t   fused_max; /* msg sizes <= this take the fused kernel    */
     int      gated_blocks; /* gated kernel grid size (team constant)  */
+    int      zc_stream;    /* tl_cdna4::ZcStreamKnob (ZC_STREAM)       */
     bool     ce_alltoall;  /* SDMA copy-engine alltoall data path     */
     size_t   ce_alltoall_min; /* min total msg bytes for the CE path  */
     bool     p2p;        /* device active-set bcast (p2p send/recv)      */
@@ -2776,35 +2780,39 @@ class GatedCollTask final : public Cdna4Task {
             (ct_ == UCC_COLL_TYPE_ALLREDUCE ||
              ct_ == UCC_COLL_TYPE_REDUCE_SCATTER || rooted) &&
             Config::instance().get_bool("TL_CDNA4", "ZC_FUSED", true);
-        /* grid size, measured on the 2-proc rig. 64 blocks by default.
-         * One-kernel allreduce of 2 ranks at depth 4, the one case
-         * measured (profiles/zc_data_phase.md): 192 blocks from 128 MiB
-         * up; every 256 MiB run at 192 beat every run at 128.
+        /* grid size and cache policy of the data phase: the rule is
+         * tl_cdna4::zc_policy (zc_policy.h), measured on the 2-proc rig.
+         * 64 blocks by default, 128 from 160 MiB up for a single
+         * fragment, and for the one-kernel allreduce of 2 ranks at
+         * depth 4 from 128 MiB up 192 blocks and the streamed
+         * (non-temporal) data phase (profiles/zc_data_phase.md,
+         * profiles/zc_edges_stream.md).
          * Residency: all blocks of a rank spin at entry until every
          * peer's block 0 has run, so the ranks' grids must fit the card
-         * together. Every U = 4 instantiation of k_zc_allreduce
-         * compiles to at least 2 waves/SIMD (VGPRs + AGPRs), i.e. 2
-         * blocks of 256 threads per CU, 512 per card, and 192 is below
-         * half of that. It does NOT hold at U = 2: the int8/uint8
-         * instantiations there take 256 VGPRs plus AGPRs, 1 block per
-         * CU, 256 per card, so 3 or 4 ranks of 192 blocks on one card
-         * could not all be placed. Hence the conditions on n_ and on
-         * the depth the launcher will pick (UCC_EC_REDUCE_DEPTH, like
-         * GATED_BLOCKS, has to agree on all ranks: B enters the
-         * ledger). Everything else keeps the earlier rule
-         * (profiles/rocprof_kernels_r02.md): 128 from 160 MiB up for a
-         * single fragment. The launch ledger accumulates BLOCK counts,
-         * so per-collective grids compose on shared (slot,parity)
-         * counters. */
-        const size_t MiB    = 1024 * 1024;
-        const bool   big_ar = zc_fused && ct_ == UCC_COLL_TYPE_ALLREDUCE &&
-                            n_ == 2 && ec_hip::zc_depth(2) == 4 &&
-                            total_ >= 128 * MiB;
-        const int nblk =
-            tt_->cfg_.gated_blocks                  ? tt_->cfg_.gated_blocks
-            : big_ar                                ? 192
-            : nfrags_ == 1 && total_ >= 160 * MiB   ? 128
-                                                    : ec_hip::kGatedBlocks;
+         * together. Every U = 4 instantiation of k_zc_allreduce, plain
+         * or streamed, compiles to at least 2 waves/SIMD (VGPRs +
+         * AGPRs; `make check-isa`), i.e. 2 blocks of 256 threads per
+         * CU, 512 per card, and 192 is below half of that. It does NOT
+         * hold at U = 2: the int8/uint8 instantiations there take 256
+         * VGPRs plus AGPRs, 1 block per CU, 256 per card, so 3 or 4
+         * ranks of 192 blocks on one card could not all be placed.
+         * Hence the rule's conditions on n and on the depth the
+         * launcher will pick (UCC_EC_REDUCE_DEPTH, like GATED_BLOCKS,
+         * has to agree on all ranks: B enters the ledger). The launch
+         * ledger accumulates BLOCK counts, so per-collective grids
+         * compose on shared (slot,parity) counters; the cache policy
+         * does not enter it. */
+        const tl_cdna4::ZcColl zct =
+            ct_ == UCC_COLL_TYPE_ALLREDUCE        ? tl_cdna4::ZC_COLL_ALLREDUCE
+            : ct_ == UCC_COLL_TYPE_REDUCE_SCATTER
+                ? tl_cdna4::ZC_COLL_REDUCE_SCATTER
+            : ct_ == UCC_COLL_TYPE_REDUCE         ? tl_cdna4::ZC_COLL_REDUCE
+            : ct_ == UCC_COLL_TYPE_BCAST          ? tl_cdna4::ZC_COLL_BCAST
+                                                  : tl_cdna4::ZC_COLL_OTHER;
+        const tl_cdna4::ZcPolicy pol = tl_cdna4::zc_policy(
+            zct, zc_fused, (int)n_, ec_hip::zc_depth((int)n_), total_,
+            nfrags_ == 1, tt_->cfg_.gated_blocks, tt_->cfg_.zc_stream);
+        const int nblk = pol.blocks;
         const uint64_t B = (uint64_t)nblk;
         for (size_t f = 0; f < nfrags_; f++) {
             const uint32_t p   = (uint32_t)(f & 1);
@@ -2892,6 +2900,8 @@ class GatedCollTask final : public Cdna4Task {
                      * signal, the last-arriving block the completion
                      * wait — same ledger as the three launches */
                     log_path("one-kernel (k_zc_allreduce)", nblk);
+                    log_policy(pol.stream);
+                    ga.zc_stream = pol.stream ? 1 : 0;
                     ga.done_host = tt_->gdone_host_ + slot_;
                     ga.done_seq  = done_seq_;
                     st = ec_hip::zc_allreduce(ga, comp_s);
@@ -2976,6 +2986,8 @@ class GatedCollTask final : public Cdna4Task {
                     if (zc_fused) {
                         log_path("one-kernel (k_zc_allreduce into the "
                                  "root's dst)", nblk);
+                        log_policy(pol.stream);
+                        ga.zc_stream     = pol.stream ? 1 : 0;
                         ga.t_gather_wait = L[1][slot_][p] + B;
                         ga.done_host     = tt_->gdone_host_ + slot_;
                         ga.done_seq      = done_seq_;
@@ -3130,6 +3142,8 @@ class GatedCollTask final : public Cdna4Task {
                     /* same kernel, zc_write = 0: my slice into my dst
                      * only, team-reduces-done wait, no phase 2 */
                     log_path("one-kernel (k_zc_allreduce)", nblk);
+                    log_policy(pol.stream);
+                    ga.zc_stream     = pol.stream ? 1 : 0;
                     ga.t_gather_wait = L[1][slot_][p] + B;
                     ga.done_host     = tt_->gdone_host_ + slot_;
                     ga.done_seq      = done_seq_;
@@ -3351,6 +3365,21 @@ class GatedCollTask final : public Cdna4Task {
                       (size_t)total_);
         }
     }
+    /* and one naming the cache policy of k_zc_allreduce's data phase:
+     * what zc_policy returned, and whether the knob had asked for more */
+    void log_policy(bool stream)
+    {
+        if (!policy_logged_) {
+            policy_logged_ = true;
+            const bool want = tt_->cfg_.zc_stream == tl_cdna4::ZC_STREAM_ON;
+            ucc_debug("cdna4 gated %s: zc data phase: %s",
+                      coll_type_name(ct_),
+                      stream ? "streaming"
+                      : want ? "plain (no streamed instantiation)"
+                             : "plain");
+        }
+    }
+    bool               policy_logged_ = false;
     int                pslot_ = -1;
     /* zero-copy persistent allreduce: peers' USER src buffers mapped
      * via HIP-IPC (handles exchanged through the scratch channel at
@@ -3921,6 +3950,11 @@ class Cdna4Tl final : public Tl {
         cfg.declare("TL_CDNA4", "ZC_FUSED", "1",
                     "zero-copy allreduce/reduce_scatter as one kernel "
                     "per post; 0 = stage/reduce/gather launches (debug)");
+        cfg.declare("TL_CDNA4", "ZC_STREAM", "auto",
+                    "non-temporal (streaming) data phase of the one-kernel "
+                    "zero-copy allreduce: auto = 2 ranks from 128 MiB, "
+                    "0 = never, 1 = wherever a streamed kernel exists "
+                    "(depth 4), reduce_scatter and reduce included");
         cfg.declare("TL_CDNA4", "PUSH", "1",
                     "push-model gated flags; 0 = remote-poll fallback "
                     "(debug)");
@@ -4007,6 +4041,12 @@ class Cdna4Tl final : public Tl {
             (uint64_t)cfg.get_int("TL_CDNA4", "SPIN_LIMIT", 0);
         c.fused_max = cfg.get_size("TL_CDNA4", "FUSED_MAX",
                                    4 * 1024 * 1024);
+        {
+            const std::string zs = cfg.get("TL_CDNA4", "ZC_STREAM", "auto");
+            c.zc_stream = zs == "0"   ? tl_cdna4::ZC_STREAM_OFF
+                          : zs == "1" ? tl_cdna4::ZC_STREAM_ON
+                                      : tl_cdna4::ZC_STREAM_AUTO;
+        }
         c.gated_blocks =
             (int)cfg.get_int("TL_CDNA4", "GATED_BLOCKS", 0);
         if (c.gated_blocks < 0) {
