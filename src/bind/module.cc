@@ -829,6 +829,66 @@ PYBIND11_MODULE(_core, m)
         },
         py::arg("pieces"), py::arg("dt"), py::arg("op"), py::arg("alpha"),
         py::arg("in_acc"), py::arg("out_acc"), py::arg("blocks") = 0);
+    /* kernel unit-test hook: one gather_copy launch on the null stream,
+     * in-process, synchronised: dst_base + offs[i] <- srcs[i], lens[i]
+     * bytes. Returns the grid it used. ec_gather_copy_blocks is that grid
+     * alone: host code, callable without a device. */
+    auto gather_args = [](const char *who, uintptr_t dst_base,
+                          const std::vector<uintptr_t> &srcs,
+                          const std::vector<uint64_t>  &offs,
+                          const std::vector<uint64_t>  &lens) {
+        const size_t n = lens.size();
+        if (n < 1 || n > (size_t)ucc::ec_hip::kMaxSrcs ||
+            srcs.size() != n || offs.size() != n) {
+            throw std::runtime_error(
+                std::string(who) + ": 1.." +
+                std::to_string(ucc::ec_hip::kMaxSrcs) +
+                " sources, and srcs, offs, lens of one length");
+        }
+        ucc::ec_hip::GatherArgs a{};
+        a.dst_base = (void *)dst_base;
+        a.n        = (int)n;
+        for (size_t i = 0; i < n; i++) {
+            a.srcs[i] = (const void *)srcs[i];
+            a.offs[i] = offs[i];
+            a.lens[i] = lens[i];
+        }
+        return a;
+    };
+    m.def(
+        "ec_gather_copy",
+        [gather_args](uintptr_t dst_base, std::vector<uintptr_t> srcs,
+                      std::vector<uint64_t> offs,
+                      std::vector<uint64_t> lens) {
+            const ucc::ec_hip::GatherArgs a =
+                gather_args("ec_gather_copy", dst_base, srcs, offs, lens);
+            for (int i = 0; i < a.n; i++) {
+                if (a.lens[i] && (!a.dst_base || !a.srcs[i])) {
+                    throw std::runtime_error(
+                        "ec_gather_copy: null pointer with a length");
+                }
+            }
+            int blocks = 0;
+            check(ucc::ec_hip::gather_copy(a, nullptr, &blocks),
+                  "gather_copy");
+            const hipError_t he = hipDeviceSynchronize();
+            if (he != hipSuccess) {
+                throw std::runtime_error(std::string("ec_gather_copy: ") +
+                                         hipGetErrorString(he));
+            }
+            return blocks;
+        },
+        py::arg("dst_base"), py::arg("srcs"), py::arg("offs"),
+        py::arg("lens"));
+    m.def(
+        "ec_gather_copy_blocks",
+        [gather_args](std::vector<uint64_t> lens) {
+            const std::vector<uintptr_t> srcs(lens.size(), 0);
+            const std::vector<uint64_t>  offs(lens.size(), 0);
+            return ucc::ec_hip::gather_copy_blocks(gather_args(
+                "ec_gather_copy_blocks", 0, srcs, offs, lens));
+        },
+        py::arg("lens"));
     m.def("ec_ring_step_launches",
           []() { return ucc::ec_hip::ring_step_launches(); });
     m.def("hip_device_count",

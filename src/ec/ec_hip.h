@@ -45,7 +45,15 @@ struct GatherArgs {
     uint64_t    lens[kMaxSrcs];
     int         n;
 };
-ucc_status_t gather_copy(const GatherArgs &a, hipStream_t stream);
+/* blocks_used, if given, receives the grid that was launched */
+ucc_status_t gather_copy(const GatherArgs &a, hipStream_t stream,
+                         int *blocks_used = nullptr);
+/* The grid gather_copy() launches for these arguments (256 threads per
+ * block): sized from the total bytes, which the kernel then deals evenly
+ * over the sources. Reads n and lens only; pure host code, no device
+ * needed. The copy tests take the grid from here to work out which loops
+ * of the kernel a case reaches. */
+int gather_copy_blocks(const GatherArgs &a);
 
 /* Fused small-message allreduce: one kernel per rank that stages src into
  * its scratch, signals arrival on every peer's flag array (system-scope),

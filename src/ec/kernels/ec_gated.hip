@@ -318,7 +318,19 @@ __global__ void k_staged_gather(const GatedArgs a)
     const int grp = gridDim.x / a.nranks > 0 ? gridDim.x / a.nranks : 1;
     const int src = (int)blockIdx.x / grp;
     const int bid = (int)blockIdx.x % grp;
-    if (src < a.nranks) {
+    if ((int)gridDim.x < a.nranks) {
+        /* fewer blocks than sources (a small GATED_BLOCKS): each block
+         * takes whole sources in turn, as k_gather_copy does. Every block
+         * still signals exactly once below. */
+        for (int s = (int)blockIdx.x; s < a.nranks; s += (int)gridDim.x) {
+            uint64_t b = a.slice_b[s], e = a.slice_e[s];
+            if (e > b) {
+                d_copy_bytes_part((uint8_t *)a.dst + b,
+                                  (const uint8_t *)a.peer_out[s], e - b, 0,
+                                  1);
+            }
+        }
+    } else if (src < a.nranks) {
         uint64_t b = a.slice_b[src], e = a.slice_e[src];
         if (e > b) {
             d_copy_bytes_part((uint8_t *)a.dst + b,

@@ -101,19 +101,31 @@ ucc_status_t reduce(const ReduceArgs &a_in, hipStream_t s)
     return dispatch<LaunchReduce>(a.dt, a.op, a, s);
 }
 
-ucc_status_t gather_copy(const GatherArgs &a, hipStream_t s)
+constexpr int kGatherThreads = 256;
+
+int gather_copy_blocks(const GatherArgs &a)
 {
     uint64_t total = 0;
     for (int i = 0; i < a.n; i++) {
         total += a.lens[i];
     }
-    int threads = 256;
-    int blocks =
-        (int)std::min<uint64_t>((total / 16 + threads - 1) / threads, 2048);
+    int blocks = (int)std::min<uint64_t>(
+        (total / 16 + kGatherThreads - 1) / kGatherThreads, 2048);
     if (blocks < 1) {
         blocks = 1;
     }
-    hipLaunchKernelGGL(k_gather_copy, dim3(blocks), dim3(threads), 0, s, a);
+    return blocks;
+}
+
+ucc_status_t gather_copy(const GatherArgs &a, hipStream_t s,
+                         int *blocks_used)
+{
+    const int blocks = gather_copy_blocks(a);
+    hipLaunchKernelGGL(k_gather_copy, dim3(blocks), dim3(kGatherThreads), 0,
+                       s, a);
+    if (blocks_used) {
+        *blocks_used = blocks;
+    }
     return launch_status();
 }
 

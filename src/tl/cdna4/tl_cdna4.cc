@@ -1357,6 +1357,8 @@ class StagedTask final : public Cdna4Task {
             break;
         }
         case UCC_COLL_TYPE_ALLTOALL: {
+            /* in place is already refused at init (inplace_alltoall);
+             * kept as a second guard for a task built another way */
             if (inplace || cell_ == 0) {
                 return UCC_ERR_NOT_SUPPORTED;
             }
@@ -1374,6 +1376,8 @@ class StagedTask final : public Cdna4Task {
             break;
         }
         case UCC_COLL_TYPE_ALLTOALLV: {
+            /* in place is already refused at init (inplace_alltoall);
+             * kept as a second guard for a task built another way */
             if (inplace || cell_ == 0) {
                 return UCC_ERR_NOT_SUPPORTED;
             }
@@ -2174,6 +2178,8 @@ class GatedCollTask final : public Cdna4Task {
             break;
         }
         case UCC_COLL_TYPE_ALLTOALL: {
+            /* in place is already refused at init (inplace_alltoall);
+             * kept as a second guard for a task built another way */
             if (inplace || cell_ == 0) {
                 return UCC_ERR_NOT_SUPPORTED;
             }
@@ -2194,6 +2200,8 @@ class GatedCollTask final : public Cdna4Task {
              * before any fragment is enqueued. Rank i's send cell to j
              * and its gather of j's cell both clip to the locally-known
              * lengths; empty tails still launch and signal. */
+            /* in place is already refused at init (inplace_alltoall);
+             * kept as a second guard for a task built another way */
             if (inplace || cell_ == 0) {
                 return UCC_ERR_NOT_SUPPORTED;
             }
@@ -3193,6 +3201,7 @@ class GatedCollTask final : public Cdna4Task {
                 const bool agzc = zc_ && zc_ready_;
                 if (agzc) {
                     ga.len = 0; /* stage = pure signal */
+                    log_path("gather from the peers' user src", (int)B);
                 }
                 for (uint32_t r = 0; r < n_; r++) {
                     ga.peer_out[r] =
@@ -3289,6 +3298,7 @@ class GatedCollTask final : public Cdna4Task {
                 ga.n_cells = a2zc ? 0 : (int)n_;
                 if (a2zc) {
                     ga.len = 0; /* stage = pure signal */
+                    log_path("gather from the peers' user src", (int)B);
                 }
                 for (uint32_t r = 0; r < n_; r++) {
                     ga.c_src_off[r] = (uint64_t)r * out_b_ + off;
@@ -3938,7 +3948,10 @@ class Cdna4Tl final : public Tl {
                     "device spin bound override (0 = default ~seconds)");
         cfg.declare("TL_CDNA4", "GATED_BLOCKS", "0",
                     "gated-pipeline kernel grid size (workgroups of 256; "
-                    "0 = built-in default; must match on every rank)");
+                    "0 = built-in default; must match on every rank). Any "
+                    "value >= 1 is correct at any team size, also a grid "
+                    "smaller than the team: the gather kernel's blocks "
+                    "then take whole sources in turn");
         cfg.declare("TL_CDNA4", "STAGE_SDMA", "0",
                     "stage fragments with hipMemcpyAsync (SDMA) "
                     "instead of a copy kernel");
@@ -4089,11 +4102,23 @@ static Cdna4Tl g_cdna4_tl;
 
 Tl *Cdna4TlContext::iface() { return &g_cdna4_tl; }
 
+/* alltoall(v) in place has no staged or gated form: refused when the
+ * request is initialised, not when it is posted */
+static bool inplace_alltoall(const ucc_coll_args_t &args)
+{
+    return (args.coll_type == UCC_COLL_TYPE_ALLTOALL ||
+            args.coll_type == UCC_COLL_TYPE_ALLTOALLV) &&
+           (args.flags & UCC_COLL_ARGS_FLAG_IN_PLACE);
+}
+
 ucc_status_t Cdna4TlTeam::init_gated(const ucc_coll_args_t &args, Team *t,
                                      Task **task)
 {
     if (args.mask & UCC_COLL_ARGS_FIELD_ACTIVE_SET) {
         return UCC_ERR_NOT_SUPPORTED; /* active_set_p2p only */
+    }
+    if (inplace_alltoall(args)) {
+        return UCC_ERR_NOT_SUPPORTED;
     }
     if (args.coll_type == UCC_COLL_TYPE_ALLREDUCE ||
         args.coll_type == UCC_COLL_TYPE_REDUCE_SCATTER ||
@@ -4129,6 +4154,9 @@ ucc_status_t Cdna4TlTeam::init_staged(const ucc_coll_args_t &args, Team *t,
     /* subset colls never take the team-wide slot sequence: non-members
      * post nothing (active_set_p2p serves bcast) */
     if (args.mask & UCC_COLL_ARGS_FIELD_ACTIVE_SET) {
+        return UCC_ERR_NOT_SUPPORTED;
+    }
+    if (inplace_alltoall(args)) {
         return UCC_ERR_NOT_SUPPORTED;
     }
     /* reductions need a supported dtype x op on device */
