@@ -42,7 +42,8 @@ PERFTEST := build/ucc_perftest
 INFO     := build/ucc_info
 NTESTS   := build/test_generic_dt build/test_obj_size build/test_mt \
             build/test_p2p_mbox build/test_ring_plan build/test_fused_plan \
-            build/test_fused_plan_v build/test_zc_policy
+            build/test_fused_plan_v build/test_fused_plan_rooted \
+            build/test_zc_policy
 
 all: $(MODULE) $(SHLIB) $(PERFTEST) $(INFO) $(NTESTS)
 
@@ -73,6 +74,10 @@ build/test_fused_plan: $(BUILD)/tests/test_fused_plan.o
 
 # host-only: the v-forms of the same header
 build/test_fused_plan_v: $(BUILD)/tests/test_fused_plan_v.o
+	$(HIPCC) $^ -o $@
+
+# host-only: gather, scatter, gatherv and scatterv of the same header
+build/test_fused_plan_rooted: $(BUILD)/tests/test_fused_plan_rooted.o
 	$(HIPCC) $^ -o $@
 
 # host-only: the grid / cache-policy rule header and nothing else
@@ -176,6 +181,10 @@ build/asan_fused_plan: tests/native/test_fused_plan.cc src/tl/cdna4/fused_plan.h
 	$(HIPCC) -x c++ -std=c++17 -O1 -g -fsanitize=address,undefined \
 	    -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< -o $@
 
+build/asan_fused_plan_rooted: tests/native/test_fused_plan_rooted.cc src/tl/cdna4/fused_plan.h
+	$(HIPCC) -x c++ -std=c++17 -O1 -g -fsanitize=address,undefined \
+	    -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< -o $@
+
 build/asan_zc_policy: tests/native/test_zc_policy.cc src/tl/cdna4/zc_policy.h
 	$(HIPCC) -x c++ -std=c++17 -O1 -g -fsanitize=address,undefined \
 	    -fno-sanitize-recover=undefined -fno-omit-frame-pointer $< -o $@
@@ -183,11 +192,12 @@ build/asan_zc_policy: tests/native/test_zc_policy.cc src/tl/cdna4/zc_policy.h
 .PHONY: asan
 asan: build/asan_generic_dt build/asan_obj_size build/asan_perftest \
       build/asan_p2p_mbox build/asan_ring_plan build/asan_fused_plan \
-      build/asan_zc_policy
+      build/asan_fused_plan_rooted build/asan_zc_policy
 	ASAN_OPTIONS=detect_leaks=1 ./build/asan_zc_policy
 	ASAN_OPTIONS=detect_leaks=1 ./build/asan_p2p_mbox
 	ASAN_OPTIONS=detect_leaks=1 ./build/asan_ring_plan
 	ASAN_OPTIONS=detect_leaks=1 ./build/asan_fused_plan
+	ASAN_OPTIONS=detect_leaks=1 ./build/asan_fused_plan_rooted
 	ASAN_OPTIONS=detect_leaks=1 ./build/asan_obj_size
 	ASAN_OPTIONS=detect_leaks=1 ./build/asan_generic_dt
 	for cl in allreduce bcast alltoall alltoallv reduce_scatter barrier; do \

@@ -195,6 +195,44 @@ struct FusedA2avArgs {
 };
 ucc_status_t fused_a2av(const FusedA2avArgs &a, hipStream_t stream);
 
+/* Fused small-message gather and scatter run fused_coll() /
+ * fused_coll_graph() with their plans (fused_plan.h). gatherv and scatterv
+ * (k_fused_rooted_v, host-sequenced only): the counts are known at the root
+ * only, so the root publishes its verdict, and for scatterv where each
+ * rank's block lies, in a header at offset 0 of its scratch: word 0 the
+ * verdict, then nranks entries (scratch_off, len), two u64 at 16 + 16 * r
+ * (kRootedHdrBytes bytes in all; the cells lie behind it).
+ *   1. at the root, thread 0 of block 0 stores the table (tab_off, tab_len),
+ *      then the verdict 2 * seq + fits_local; every rank whose fits_local is
+ *      set stages its c.n_cells cells
+ *   2. the handshake of fused_coll, whatever was voted
+ *   3. every block reads word 0 of the root's header: "fits" iff it is
+ *      2 * seq + 1; a non-root of scatterv then reads its entry
+ *   4. "fits": the root of gatherv, and the root of a not-in-place scatterv,
+ *      copy their c.n_segs segments; a non-root of scatterv copies
+ *      min(entry len, my_len) bytes from the root's scratch + entry off to
+ *      dst, or nothing if the entry does not lie 16-byte aligned inside
+ *      [kRootedHdrBytes, kRootedHdrBytes + bound]. Otherwise dst is not
+ *      touched.
+ *   5. completion as fused_a2av: 2 * done_seq + verdict to *verdict_host,
+ *      then the release store of the completion word.
+ * No rank reads or writes a scratch byte at or past kRootedHdrBytes + bound
+ * or a dst byte past its own plan, whatever the other ranks' counts: the
+ * launcher refuses cells and segments that leave the area. c is a plan of
+ * fused_plan_init_rooted_v; c.r_count must be 0. */
+constexpr uint64_t kRootedHdrBytes = 16 + 16 * (uint64_t)kMaxRanks;
+struct FusedRootedVArgs {
+    FusedCollArgs c;
+    int           root;
+    int           is_scatter;
+    int           fits_local;
+    uint64_t      my_len; /* scatterv non-root: bytes my dst holds        */
+    uint64_t      bound;  /* B of fused_plan.h                            */
+    uint64_t      tab_off[kMaxRanks], tab_len[kMaxRanks]; /* root only    */
+    uint64_t     *verdict_host;
+};
+ucc_status_t fused_rooted_v(const FusedRootedVArgs &a, hipStream_t stream);
+
 bool dt_supported(ucc_datatype_t dt);
 bool op_supported(ucc_datatype_t dt, ucc_reduction_op_t op);
 

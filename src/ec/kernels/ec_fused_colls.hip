@@ -3,8 +3,9 @@
  * and graph-capturable (k_fused_coll_graph). One body, two kernels; the
  * sequencing, handshake and completion steps are the fused allreduce's
  * (ec_device.h, "fused one-kernel protocol"). allgatherv and
- * reduce_scatterv run the same kernels with another plan; alltoallv has the
- * host-sequenced k_fused_a2av at the end of this file. */
+ * reduce_scatterv, gather and scatter run the same kernels with another
+ * plan; alltoallv has the host-sequenced k_fused_a2av, gatherv and scatterv
+ * the host-sequenced k_fused_rooted_v, at the end of this file. */
 #include "ec_device.h"
 
 namespace ucc {
@@ -220,6 +221,139 @@ ucc_status_t fused_a2av(const FusedA2avArgs &a, hipStream_t s)
         return UCC_ERR_INVALID_PARAM;
     }
     hipLaunchKernelGGL(k_fused_a2av, dim3(a.c.nblocks), dim3(256), 0, s, a);
+    return launch_status();
+}
+
+/* -------------------------------------------------- gatherv and scatterv */
+/* The fused gatherv / scatterv: the protocol above with the root's verdict
+ * and, for scatterv, the root's table of where each rank's block lies
+ * (FusedRootedVArgs in ec_hip.h). The only waits are the bounded ones of
+ * fused_handshake.
+ *
+ * Why every block of every rank reads this post's table and verdict: thread
+ * 0 of the root's block 0 stores the entries and then the verdict before
+ * that block's fence and arrival add, block 0 signals the peers only after
+ * all of the root's blocks arrived, and a block reads the root's header only
+ * after it saw all n signals of this seq. The verdict carries the seq, so a
+ * header left by an earlier use of the slot never reads as "fits"; the
+ * entries carry none, but they are only read behind a verdict of this seq,
+ * and the same thread stored them before it.
+ *
+ * What a non-root of scatterv reads comes from another rank, so it is
+ * checked here and not by the launcher: an entry that is not a 16-byte
+ * aligned range inside [kRootedHdrBytes, kRootedHdrBytes + bound] copies
+ * nothing, and never more than my_len bytes reach dst.
+ *
+ * `a` is the kernel's by-value argument and stays const (see the note at
+ * GatedTargets in ec_gated.hip). */
+__global__ void k_fused_rooted_v(FusedRootedVArgs a)
+{
+    const FusedCollArgs &c    = a.c;
+    const FusedIter      it   = fused_iter<false>(c);
+    uint8_t             *mysc = (uint8_t *)c.my_scratch;
+    const bool           root = c.rank == a.root;
+    /* 1. the root's table, then its verdict; then my cells */
+    if (root && blockIdx.x == 0 && threadIdx.x == 0) {
+        uint64_t *hdr = (uint64_t *)mysc;
+        for (int r = 0; r < c.nranks; r++) {
+            sys_store(hdr + 2 + 2 * r, a.tab_off[r]);
+            sys_store(hdr + 3 + 2 * r, a.tab_len[r]);
+        }
+        sys_store(hdr, 2 * it.seq + (a.fits_local ? 1 : 0));
+    }
+    if (a.fits_local) {
+        for (int k = 0; k < c.n_cells; k++) {
+            d_copy_bytes(mysc + c.c_sc_off[k],
+                         (const uint8_t *)c.src + c.c_src_off[k], c.c_len[k]);
+        }
+    }
+    /* 2. every rank takes part, whatever the root decided */
+    if (!fused_handshake(c, it)) {
+        return;
+    }
+    /* 3. the root's verdict and, for a non-root of scatterv, my entry */
+    __shared__ uint64_t s_verdict, s_off, s_len;
+    if (threadIdx.x == 0) {
+        const uint64_t *hdr = (const uint64_t *)c.peer_scratch[a.root];
+        s_verdict           = sys_load(hdr);
+        s_off = s_len = 0;
+        if (a.is_scatter && !root && s_verdict == 2 * it.seq + 1) {
+            const uint64_t off = sys_load(hdr + 2 + 2 * c.rank);
+            const uint64_t len = sys_load(hdr + 3 + 2 * c.rank);
+            const uint64_t end = kRootedHdrBytes + a.bound;
+            if (off >= kRootedHdrBytes && (off & 15) == 0 && off <= end &&
+                len <= end - off) {
+                s_off = off;
+                s_len = len < a.my_len ? len : a.my_len;
+            }
+        }
+    }
+    __syncthreads();
+    const bool fits = s_verdict == 2 * it.seq + 1;
+    /* 4. my copies, or nothing */
+    if (fits) {
+        if (a.is_scatter && !root) {
+            d_copy_bytes((uint8_t *)c.dst,
+                         (const uint8_t *)c.peer_scratch[a.root] + s_off,
+                         s_len);
+        } else {
+            for (int k = 0; k < c.n_segs; k++) {
+                d_copy_bytes((uint8_t *)c.dst + c.g_dst_off[k],
+                             (const uint8_t *)c.peer_scratch[c.g_peer[k]] +
+                                 c.g_sc_off[k],
+                             c.g_len[k]);
+            }
+        }
+    }
+    /* 5. as k_fused_a2av: the verdict, then the release of the done word */
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t v = __hip_atomic_fetch_add(
+                         c.local_flags + kFusedDoneBase + c.slot, 1,
+                         __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) +
+                     1;
+        if (v == c.done_target) {
+            sys_store(a.verdict_host, 2 * c.done_seq + (fits ? 1 : 0));
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __hip_atomic_store(c.done_host, c.done_seq, __ATOMIC_RELEASE,
+                               __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+/* validates like fused_a2av(), and that no cell and no segment leaves the
+ * header + bound area of a scratch: the kernel trusts them */
+ucc_status_t fused_rooted_v(const FusedRootedVArgs &a, hipStream_t s)
+{
+    const uint64_t end = kRootedHdrBytes + a.bound;
+    if (!fused_coll_args_ok(a.c, 1024) || a.c.r_count != 0 ||
+        !a.verdict_host || !a.c.done_host || a.root < 0 ||
+        a.root >= a.c.nranks || a.bound < 16 || (a.bound & 15) != 0 ||
+        a.bound > (UINT64_MAX >> 8)) {
+        return UCC_ERR_INVALID_PARAM;
+    }
+    for (int k = 0; k < a.c.n_cells; k++) {
+        if (a.c.c_sc_off[k] < kRootedHdrBytes || (a.c.c_sc_off[k] & 15) != 0 ||
+            a.c.c_sc_off[k] > end || a.c.c_len[k] > end - a.c.c_sc_off[k]) {
+            return UCC_ERR_INVALID_PARAM;
+        }
+    }
+    /* a non-root of scatterv takes its one segment from the root's table */
+    const bool table_seg = a.is_scatter && a.c.rank != a.root;
+    if (table_seg ? a.c.n_segs > 1
+                  : a.c.n_segs > 0 && a.c.rank != a.root) {
+        return UCC_ERR_INVALID_PARAM;
+    }
+    for (int k = 0; !table_seg && k < a.c.n_segs; k++) {
+        if (a.c.g_peer[k] < 0 || a.c.g_peer[k] >= a.c.nranks ||
+            a.c.g_sc_off[k] < kRootedHdrBytes || (a.c.g_sc_off[k] & 15) != 0 ||
+            a.c.g_sc_off[k] > end || a.c.g_len[k] > end - a.c.g_sc_off[k]) {
+            return UCC_ERR_INVALID_PARAM;
+        }
+    }
+    hipLaunchKernelGGL(k_fused_rooted_v, dim3(a.c.nblocks), dim3(256), 0, s,
+                       a);
     return launch_status();
 }
 

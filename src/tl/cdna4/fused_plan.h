@@ -38,7 +38,22 @@
  *
  * The ragged forms (allgatherv, reduce_scatterv, alltoallv) have an
  * initialiser of their own, fused_plan_init_v, described at its definition;
- * tests/native/test_fused_plan_v.cc runs it for all ranks. */
+ * tests/native/test_fused_plan_v.cc runs it for all ranks.
+ *
+ * The rooted copy collectives (UCC_TL_CDNA4_FUSED_GATHER_SCATTER). gather and
+ * scatter are two more plans of fused_plan_init:
+ *   gather          cell 0 = my block, on every rank; the root has n
+ *                   segments, peer r's cell 0 -> dst + r * block; a non-root
+ *                   has none
+ *   scatter         cell d = the root's block for rank d, at the root only;
+ *                   rank r has one segment, the root's cell r -> dst + 0
+ * In place is significant at the root only (StagedTask::post()'s rules) and
+ * is ignored elsewhere: a gather root stages nothing and has no segment for
+ * itself, its block already lies at dst + root * block; a scatter root makes
+ * no cell and no segment for itself, its block stays in src.
+ * gatherv and scatterv, whose counts only the root knows, have
+ * fused_plan_init_rooted_v at the end of this file;
+ * tests/native/test_fused_plan_rooted.cc runs all four for all ranks. */
 #ifndef UCC_AMD_FUSED_PLAN_H_
 #define UCC_AMD_FUSED_PLAN_H_
 
@@ -53,7 +68,11 @@ enum FusedColl { FUSED_ALLGATHER = 0, FUSED_REDUCE_SCATTER = 1,
                  FUSED_ALLTOALL = 2, FUSED_BCAST = 3, FUSED_REDUCE = 4,
                  /* v-forms: fused_plan_init_v below */
                  FUSED_ALLGATHERV = 5, FUSED_REDUCE_SCATTERV = 6,
-                 FUSED_ALLTOALLV = 7 };
+                 FUSED_ALLTOALLV = 7,
+                 /* rooted copies: fused_plan_init (gather, scatter) and
+                  * fused_plan_init_rooted_v (gatherv, scatterv) */
+                 FUSED_GATHER = 8, FUSED_SCATTER = 9, FUSED_GATHERV = 10,
+                 FUSED_SCATTERV = 11 };
 
 struct FusedCell {
     uint64_t src_off = 0, scratch_off = 0, len = 0; /* bytes */
@@ -81,6 +100,11 @@ struct FusedPlan {
     /* alltoallv only */
     uint64_t  cell_bytes = 0;  /* the fixed cell size                     */
     bool      fits_local = true; /* my vote: all my send lengths <= cell  */
+    /* gatherv / scatterv only (fused_plan_init_rooted_v) */
+    uint64_t  bound = 0;       /* B: no scratch access at or past 144 + B  */
+    uint64_t  my_len = 0;      /* bytes of my own block                    */
+    /* the root's table, (scratch_off, len) per rank */
+    uint64_t  tab_off[kFusedMaxRanks] = {}, tab_len[kFusedMaxRanks] = {};
 };
 
 static inline uint64_t fused_plan_stride(uint64_t block_bytes)
@@ -93,9 +117,11 @@ static inline uint64_t fused_plan_stride(uint64_t block_bytes)
 static inline uint64_t fused_plan_scratch_bytes(FusedColl coll, int n,
                                                 uint64_t block_bytes)
 {
-    const uint64_t cells =
-        coll == FUSED_REDUCE_SCATTER || coll == FUSED_ALLTOALL ? (uint64_t)n
-                                                               : 1;
+    const uint64_t cells = coll == FUSED_REDUCE_SCATTER ||
+                                   coll == FUSED_ALLTOALL ||
+                                   coll == FUSED_SCATTER
+                               ? (uint64_t)n
+                               : 1;
     return cells * fused_plan_stride(block_bytes);
 }
 
@@ -179,6 +205,42 @@ static inline bool fused_plan_init(FusedPlan *p, FusedColl coll, int n,
             p->red_count = b / elem_size;
         }
         break;
+    case FUSED_GATHER: {
+        const bool ip = inplace && rank == root;
+        if (!ip) {
+            p->n_cells     = 1;
+            p->cell[0].len = b;
+        }
+        for (int r = 0; rank == root && r < n; r++) {
+            if (ip && r == root) {
+                continue;
+            }
+            FusedSeg &s = p->seg[p->n_segs++];
+            s.peer      = r;
+            s.dst_off   = (uint64_t)r * b;
+            s.len       = b;
+        }
+        break;
+    }
+    case FUSED_SCATTER: {
+        const bool ip = inplace && rank == root;
+        for (int d = 0; rank == root && d < n; d++) {
+            if (ip && d == root) {
+                continue;
+            }
+            FusedCell &c  = p->cell[p->n_cells++];
+            c.src_off     = (uint64_t)d * b;
+            c.scratch_off = (uint64_t)d * stride;
+            c.len         = b;
+        }
+        if (!ip) {
+            p->n_segs             = 1;
+            p->seg[0].peer        = root;
+            p->seg[0].scratch_off = me * stride;
+            p->seg[0].len         = b;
+        }
+        break;
+    }
     default: return false;
     }
     for (int c = 0; c < p->n_cells; c++) {
@@ -394,6 +456,177 @@ static inline bool fused_plan_a2av_verdict(const bool *votes, int n)
     for (int r = 0; r < n; r++) {
         if (!votes[r]) {
             return false;
+        }
+    }
+    return true;
+}
+
+/* ------------------------------------------------- gatherv and scatterv
+ * The counts are significant at the root only, so no rank but the root can
+ * tell whether a request fits, and a non-root of scatterv does not know
+ * where its block lies in the root's scratch. The root says both in a header
+ * at offset 0 of ITS scratch (only the root's header is ever read):
+ *   word 0            the root's verdict, 2 * seq + fits (k_fused_rooted_v)
+ *   16 + 16 * r       rank r's entry, two u64: (scratch_off, len)
+ * kFusedRootedHdr = 16 + 16 * kFusedMaxRanks bytes; the cells follow.
+ *
+ * B = fused_plan_rooted_v_bound(bound): what is left of `bound` (the knob,
+ * capped by the staging chunk: equal on every rank) after the header, rounded
+ * down to 16. scratch_bytes = header + B on every rank, and no access of any
+ * rank, whatever the other ranks' counts, touches a byte at or past it.
+ *
+ *   gatherv   every rank with a non-zero block of at most B bytes stages it
+ *             into the one cell at the header's end; a longer block is not
+ *             staged. Root: segment r = counts[r] bytes of peer r's cell ->
+ *             dst + displs[r]; zero counts are skipped, and the root's own
+ *             when in place (the block already lies at dst + displs[root]).
+ *             The root fits iff every counts[r] <= B: the bound is on the
+ *             largest block, as for allgatherv.
+ *   scatterv  root: cell d at header + the running sum of stride(counts[k]),
+ *             k < d, from src + displs[d]; zero counts, and the root's own
+ *             when in place (the block stays in src), make no cell. The
+ *             table holds these offsets and lengths. The root fits iff the
+ *             sum of all strides <= B: the bound is on the sum, as for
+ *             reduce_scatterv. A root that does not fit stages nothing. A
+ *             non-root has one segment of my_len bytes from the root's
+ *             scratch to dst + 0 whose scratch offset is NOT in the plan
+ *             (scratch_off stays 0): the kernel reads it, and the length the
+ *             root meant, from the root's table. A root not in place reads
+ *             its own cell, min(counts[root], my_len) bytes.
+ * counts / displs: bytes, read at the root only (may be null elsewhere).
+ * my_len: bytes of my own block, a non-root's src (gatherv) resp. every
+ * not-in-place rank's dst (scatterv); a gatherv root's own length is
+ * counts[root]. fits_local: at the root the verdict; at a gatherv non-root
+ * whether it staged (my_len <= B). */
+constexpr uint64_t kFusedRootedHdr = 16 + 16 * (uint64_t)kFusedMaxRanks;
+
+/* B from the rank-invariant bound; 0: no room */
+static inline uint64_t fused_plan_rooted_v_bound(uint64_t bound)
+{
+    return bound < kFusedRootedHdr + 16
+               ? 0
+               : (bound - kFusedRootedHdr) & ~(uint64_t)15;
+}
+
+/* false: not expressible (rank count, rank, root, a count that is no
+ * multiple of the element size, all counts zero at the root, B < 16) */
+static inline bool fused_plan_init_rooted_v(FusedPlan *p, FusedColl coll,
+                                            int n, int rank, int root,
+                                            const uint64_t *counts,
+                                            const uint64_t *displs,
+                                            uint64_t my_len, uint64_t B,
+                                            size_t elem_size, bool inplace)
+{
+    if (n < 2 || n > kFusedMaxRanks || rank < 0 || rank >= n || root < 0 ||
+        root >= n || elem_size == 0 || B < 16 || B % 16 != 0 ||
+        B > (UINT64_MAX >> 8) ||
+        (coll != FUSED_GATHERV && coll != FUSED_SCATTERV) ||
+        (rank == root && (!counts || !displs))) {
+        return false;
+    }
+    *p               = FusedPlan{};
+    p->coll          = coll;
+    p->n             = n;
+    p->rank          = rank;
+    p->root          = root;
+    p->bound         = B;
+    p->scratch_bytes = kFusedRootedHdr + B;
+    const bool is_root = rank == root;
+    const bool ip      = inplace && is_root;
+    if (is_root) {
+        uint64_t any = 0, sum = 0;
+        bool     each_fits = true;
+        for (int r = 0; r < n; r++) {
+            if (counts[r] % elem_size != 0) {
+                return false;
+            }
+            any |= counts[r];
+            each_fits = each_fits && counts[r] <= B;
+            /* saturate: the strides of 8 counts near 2^64 must not wrap */
+            sum = counts[r] > B || sum > B ? B + 16
+                                           : sum + fused_plan_stride(counts[r]);
+        }
+        if (!any) {
+            return false;
+        }
+        p->fits_local = coll == FUSED_GATHERV ? each_fits : sum <= B;
+    } else if (my_len % elem_size != 0) {
+        return false;
+    }
+    if (coll == FUSED_GATHERV) {
+        p->my_len = is_root ? counts[root] : my_len;
+        if (!is_root) {
+            p->fits_local = p->my_len <= B;
+        }
+        if (p->fits_local && !ip && p->my_len && p->my_len <= B) {
+            p->n_cells             = 1;
+            p->cell[0].scratch_off = kFusedRootedHdr;
+            p->cell[0].len         = p->my_len;
+        }
+        for (int r = 0; is_root && r < n; r++) {
+            p->tab_off[r] = kFusedRootedHdr;
+            p->tab_len[r] = ip && r == root ? 0 : counts[r];
+            if (!p->fits_local || !counts[r] || (ip && r == root)) {
+                continue;
+            }
+            FusedSeg &s   = p->seg[p->n_segs++];
+            s.peer        = r;
+            s.scratch_off = kFusedRootedHdr;
+            s.dst_off     = displs[r];
+            s.len         = counts[r];
+        }
+    } else {
+        p->my_len = ip ? 0 : my_len;
+        uint64_t sc = kFusedRootedHdr;
+        for (int d = 0; is_root && p->fits_local && d < n; d++) {
+            p->tab_off[d] = sc;
+            if (counts[d] && !(ip && d == root)) {
+                FusedCell &c  = p->cell[p->n_cells++];
+                c.src_off     = displs[d];
+                c.scratch_off = sc;
+                c.len         = counts[d];
+                p->tab_len[d] = counts[d];
+            }
+            sc += fused_plan_stride(counts[d]);
+        }
+        const uint64_t own =
+            !is_root ? p->my_len
+                     : (counts[root] < p->my_len ? counts[root] : p->my_len);
+        if (own && (!is_root || p->fits_local)) {
+            p->n_segs             = 1;
+            p->seg[0].peer        = root;
+            p->seg[0].scratch_off = is_root ? p->tab_off[root] : 0;
+            p->seg[0].len         = own;
+        }
+    }
+    for (int c = 0; c < p->n_cells; c++) {
+        p->stage_bytes += p->cell[c].len;
+    }
+    for (int s = 0; s < p->n_segs; s++) {
+        p->read_bytes += p->seg[s].len;
+    }
+    return true;
+}
+
+/* what k_fused_rooted_v decides and does after the handshake, from the
+ * root's plan alone: "fits" is the root's fits_local, and a scatterv
+ * non-root whose dst holds my_len bytes copies *len bytes from *off of the
+ * root's scratch. An entry that leaves the header + B area copies nothing. */
+static inline bool fused_plan_rooted_v_verdict(const FusedPlan &root_plan,
+                                               int rank, uint64_t my_len,
+                                               uint64_t *off, uint64_t *len)
+{
+    *off = *len = 0;
+    if (!root_plan.fits_local) {
+        return false;
+    }
+    if (root_plan.coll == FUSED_SCATTERV && rank != root_plan.root &&
+        rank >= 0 && rank < root_plan.n) {
+        const uint64_t o = root_plan.tab_off[rank], l = root_plan.tab_len[rank];
+        const uint64_t end = kFusedRootedHdr + root_plan.bound;
+        if (o >= kFusedRootedHdr && o % 16 == 0 && o <= end && l <= end - o) {
+            *off = o;
+            *len = l < my_len ? l : my_len;
         }
     }
     return true;

@@ -24,7 +24,9 @@
  * everything else fall back per the score map. Opt-in: the fused kernel's
  * protocol for small allgather / reduce_scatter / alltoall / bcast / reduce
  * (FusedCollTask, fused_plan.h), for allgatherv / reduce_scatterv, and for
- * alltoallv with a vote inside the kernel (FusedA2avTask).
+ * alltoallv with a vote inside the kernel (FusedA2avTask); under a knob of
+ * their own, for gather / scatter (FusedCollTask) and for gatherv / scatterv
+ * with the root's verdict read inside the kernel (FusedRootedVTask).
  */
 #include <atomic>
 #include <map>
@@ -61,7 +63,8 @@ static_assert(tl_cdna4::kZcBlocksDefault == ec_hip::kGatedBlocks,
 static_assert(kRingMaxRings == ec_hip::kMaxRings &&
                   kRingMaxRanks == ec_hip::kMaxRanks,
               "ring_plan.h and ec_hip.h disagree");
-static_assert(kFusedMaxRanks == ec_hip::kMaxRanks,
+static_assert(kFusedMaxRanks == ec_hip::kMaxRanks &&
+                  kFusedRootedHdr == ec_hip::kRootedHdrBytes,
               "fused_plan.h and ec_hip.h disagree");
 
 /* v-coll count/displacement accessors honoring the 64-bit flags
@@ -118,6 +121,8 @@ struct Cdna4Cfg {
     bool     fused_colls; /* fused one-kernel ag/rs/a2a/bcast/reduce and
                              their v-forms                                */
     size_t   fused_colls_max; /* bound on the plan's scratch_bytes         */
+    bool     fused_gather_scatter; /* fused one-kernel gather / scatter and
+                                      their v-forms (same bound)           */
 };
 
 class Cdna4Tl;
@@ -813,7 +818,8 @@ class FusedCollTask final : public Cdna4Task {
     using Cdna4Task::Cdna4Task;
 
     /* what the accept / decline decision and the plan need from the
-     * arguments; everything but inplace of REDUCE is equal on every rank */
+     * arguments; everything but inplace of REDUCE, GATHER and SCATTER (set
+     * at the root only) is equal on every rank */
     struct Shape {
         FusedColl      coll;
         ucc_datatype_t dt;
@@ -828,9 +834,11 @@ class FusedCollTask final : public Cdna4Task {
     {
         return c == FUSED_ALLGATHERV || c == FUSED_REDUCE_SCATTERV;
     }
-    static bool shape(const ucc_coll_args_t &a, uint32_t n, Shape *s)
+    static bool shape(const ucc_coll_args_t &a, uint32_t n, uint32_t me,
+                      Shape *s)
     {
-        const bool inplace = a.flags & UCC_COLL_ARGS_FLAG_IN_PLACE;
+        bool       inplace = a.flags & UCC_COLL_ARGS_FLAG_IN_PLACE;
+        const bool is_root = me == (uint32_t)a.root;
         uint64_t   count;
         switch (a.coll_type) {
         case UCC_COLL_TYPE_ALLGATHERV:
@@ -878,6 +886,20 @@ class FusedCollTask final : public Cdna4Task {
             s->dt   = a.src.info.datatype;
             count   = a.src.info.count;
             break;
+        /* the rooted copies: each rank reads the side that is significant
+         * on it, and the in-place flag counts at the root only */
+        case UCC_COLL_TYPE_GATHER:
+            s->coll = FUSED_GATHER;
+            s->dt   = is_root ? a.dst.info.datatype : a.src.info.datatype;
+            count   = is_root ? a.dst.info.count / n : a.src.info.count;
+            inplace = inplace && is_root;
+            break;
+        case UCC_COLL_TYPE_SCATTER:
+            s->coll = FUSED_SCATTER;
+            s->dt   = is_root ? a.src.info.datatype : a.dst.info.datatype;
+            count   = is_root ? a.src.info.count / n : a.dst.info.count;
+            inplace = inplace && is_root;
+            break;
         default: return false;
         }
         if (!ucc_dt_is_predefined(s->dt)) {
@@ -890,13 +912,15 @@ class FusedCollTask final : public Cdna4Task {
 
     /* Rank-invariant by construction: counts, dtype, op, n, flags and knobs
      * only, never a pointer (alignment is the kernel's business). A
-     * rank-local decline would put ranks on different algorithms. */
+     * rank-local decline would put ranks on different algorithms. gather
+     * and scatter: block, n, root and knobs only; the in-place flag, which
+     * only the root sets, takes no part. */
     static bool supported(const ucc_coll_args_t &a, const Cdna4TlTeam *tt)
     {
         const uint32_t n = tt->team_->size;
         Shape          s;
         /* s.block == 0 for a v-form: every count is zero */
-        if (!shape(a, n, &s) || s.block == 0 ||
+        if (!shape(a, n, tt->team_->rank, &s) || s.block == 0 ||
             (!is_v(s.coll) && a.root >= n) ||
             (s.coll == FUSED_ALLTOALL && s.inplace)) {
             return false;
@@ -1035,7 +1059,7 @@ class FusedCollTask final : public Cdna4Task {
     ucc_status_t fill(ec_hip::FusedCollArgs *fa, FusedPlan *pl, uint32_t slot)
     {
         Shape s;
-        if (!shape(a_, n_, &s) ||
+        if (!shape(a_, n_, me_, &s) ||
             !(is_v(s.coll)
                   ? fused_plan_init_v(pl, s.coll, (int)n_, (int)me_, s.cnt,
                                       s.dsp, nullptr, nullptr, 0,
@@ -1051,6 +1075,16 @@ class FusedCollTask final : public Cdna4Task {
                                                : a_.dst.info.buffer;
         fa->dst = ubuf_dst;
         fa->src = pl->src_is_dst ? ubuf_dst : a_.src.info.buffer;
+        /* gather and scatter: a side that is not significant on this rank
+         * is never touched, the plan has no segment resp. no cell for it */
+        if (s.coll == FUSED_GATHER || s.coll == FUSED_SCATTER) {
+            if (pl->n_segs == 0) {
+                fa->dst = nullptr;
+            }
+            if (pl->n_cells == 0) {
+                fa->src = nullptr;
+            }
+        }
         fused_args_from_plan(tt_, me_, n_, slot, *pl, fa);
         fa->dt        = s.dt;
         fa->op        = a_.op == UCC_OP_AVG ? (ucc_reduction_op_t)12 : a_.op;
@@ -1227,6 +1261,226 @@ class FusedA2avTask final : public Cdna4Task {
     Task       *inner_     = nullptr;
     const char *inner_alg_ = "";
     size_t      cell_      = 0;
+};
+
+/* Fused single-kernel gatherv / scatterv (small blocks; opt-in,
+ * UCC_TL_CDNA4_FUSED_GATHER_SCATTER). The counts are significant at the root
+ * only, so the accept / decline decision cannot look at them: every request
+ * that passes supported() launches k_fused_rooted_v, the root publishes in
+ * its scratch header whether the request fits (gatherv: every block <= B;
+ * scatterv: the sum of the 16-byte strides <= B; fused_plan.h, ec_hip.h),
+ * and every rank reads that one verdict. "Fits": the kernel has done the
+ * copies. "Does not fit": no dst byte was touched, the slot is closed, and
+ * the request is served, on a fresh slot use, by the task it has with the
+ * knob unset (Cdna4TlTeam::init_unfused). Everything else is
+ * FusedA2avTask's: slot sequencing, cumulative counters, the per-slot
+ * verdict word, the timeout; and a triggered post, which cannot fall back
+ * once captured, goes to the inner task directly. */
+class FusedRootedVTask final : public Cdna4Task {
+  public:
+    using Cdna4Task::Cdna4Task;
+
+    /* B of fused_plan.h, from knobs alone */
+    static uint64_t bound_bytes(const Cdna4TlTeam *tt)
+    {
+        size_t bound = tt->cfg_.fused_colls_max;
+        if (bound > tt->cfg_.chunk) {
+            bound = tt->cfg_.chunk;
+        }
+        return fused_plan_rooted_v_bound(bound);
+    }
+
+    /* type, n, knobs and the datatype of the side that is significant on
+     * this rank: never the counts, never a pointer, never the in-place
+     * flag's effect on anything but which datatype the root reads */
+    static bool supported(const ucc_coll_args_t &a, const Cdna4TlTeam *tt)
+    {
+        const uint32_t n = tt->team_->size;
+        if ((a.coll_type != UCC_COLL_TYPE_GATHERV &&
+             a.coll_type != UCC_COLL_TYPE_SCATTERV) ||
+            n > (uint32_t)kFusedMaxRanks || a.root >= n ||
+            bound_bytes(tt) < 16) {
+            return false;
+        }
+        const bool gv      = a.coll_type == UCC_COLL_TYPE_GATHERV;
+        const bool is_root = tt->team_->rank == (uint32_t)a.root;
+        const bool inplace = a.flags & UCC_COLL_ARGS_FLAG_IN_PLACE;
+        if (!is_root) {
+            return ucc_dt_is_predefined(gv ? a.src.info.datatype
+                                           : a.dst.info.datatype);
+        }
+        return ucc_dt_is_predefined(gv ? a.dst.info_v.datatype
+                                       : a.src.info_v.datatype) &&
+               (inplace || ucc_dt_is_predefined(gv ? a.src.info.datatype
+                                                   : a.dst.info.datatype));
+    }
+
+    ucc_status_t post() override
+    {
+        begin_use();
+        status = UCC_INPROGRESS;
+        return progress();
+    }
+
+    ucc_status_t progress() override
+    {
+        if (phase_ == 0) {
+            if (!all_ge(0)) {
+                return UCC_INPROGRESS;
+            }
+            ec_hip::FusedRootedVArgs fa{};
+            FusedPlan                pl;
+            fill(&fa, &pl);
+            fused_args_from_plan(tt_, me_, n_, slot_, pl, &fa.c);
+            fa.c.seq        = fseq_;
+            fa.c.spin_limit = tt_->spin_limit();
+            /* one block per 128 KiB of the larger of staged and read
+             * bytes; the stage counter is rank-local, so grids may differ
+             * between ranks */
+            const uint64_t big = pl.stage_bytes > pl.read_bytes
+                                     ? pl.stage_bytes
+                                     : pl.read_bytes;
+            const uint64_t blocks = (big + 128 * 1024 - 1) / (128 * 1024);
+            fa.c.nblocks =
+                (int)(blocks < 1 ? 1 : blocks > 16 ? 16 : blocks);
+            if (tt_->stage_cum_.size() < tt_->cfg_.nslots) {
+                tt_->stage_cum_.assign(tt_->cfg_.nslots, 0);
+                tt_->done_cum_.assign(tt_->cfg_.nslots, 0);
+            }
+            tt_->stage_cum_[slot_] += (uint64_t)fa.c.nblocks;
+            fa.c.stage_target = tt_->stage_cum_[slot_];
+            tt_->done_cum_[slot_] += (uint64_t)fa.c.nblocks;
+            fa.c.done_target = tt_->done_cum_[slot_];
+            fa.c.done_seq    = fseq_;
+            fa.c.done_host   = tt_->done_host_ + slot_;
+            fa.verdict_host  = tt_->verdict_host_ + slot_;
+            bound_           = (size_t)pl.bound;
+            ucc_debug("cdna4 fused %s: host-sequenced kernel "
+                      "(k_fused_rooted_v), %d blocks, bound %zu bytes",
+                      coll_type_name(a_.coll_type), fa.c.nblocks, bound_);
+            ucc_status_t st = ec_hip::fused_rooted_v(fa, comp());
+            if (st != UCC_OK) {
+                return st;
+            }
+            phase_ = 1;
+        }
+        if (phase_ == 1) {
+            if (*tt_->err_host_ != 0) {
+                ucc_error("fused %s timed out waiting for peers",
+                          coll_type_name(a_.coll_type));
+                close_slot();
+                return UCC_ERR_TIMED_OUT;
+            }
+            if (__atomic_load_n(tt_->done_host_ + slot_,
+                                __ATOMIC_ACQUIRE) < fseq_) {
+                return UCC_INPROGRESS;
+            }
+            /* stored before the completion word's release */
+            const uint64_t verdict = __atomic_load_n(
+                tt_->verdict_host_ + slot_, __ATOMIC_RELAXED);
+            close_slot();
+            if (verdict == 2 * fseq_ + 1) {
+                return UCC_OK;
+            }
+            /* every rank read the root's verdict: all fall back together */
+            ucc_status_t st = make_inner();
+            if (st != UCC_OK) {
+                return st;
+            }
+            ucc_debug("cdna4 fused %s: the counts exceed the %zu-byte "
+                      "bound, served by %s",
+                      coll_type_name(a_.coll_type), bound_, inner_alg_);
+            phase_ = 2;
+            return inner_->post();
+        }
+        if (phase_ == 2) {
+            return inner_->progress();
+        }
+        return UCC_INPROGRESS;
+    }
+
+    ucc_status_t triggered_post(void *ee_stream) override
+    {
+        ucc_status_t st = make_inner();
+        if (st != UCC_OK) {
+            return st;
+        }
+        st = inner_->triggered_post(ee_stream);
+        if (st == UCC_OK) {
+            status = inner_->status.load();
+        }
+        return st;
+    }
+
+    ~FusedRootedVTask() override { delete inner_; }
+
+  private:
+    /* The plan and the user buffers of my role. A request the plan cannot
+     * express (at the root: every count zero) still has to take part in the
+     * handshake, the other ranks cannot know: it runs an empty plan whose
+     * root votes "does not fit", and the fallback serves it. */
+    void fill(ec_hip::FusedRootedVArgs *fa, FusedPlan *pl)
+    {
+        const bool gv      = a_.coll_type == UCC_COLL_TYPE_GATHERV;
+        const bool is_root = me_ == (uint32_t)a_.root;
+        const bool inplace =
+            is_root && (a_.flags & UCC_COLL_ARGS_FLAG_IN_PLACE);
+        const uint64_t B = bound_bytes(tt_);
+        uint64_t       cnt[kFusedMaxRanks] = {}, dsp[kFusedMaxRanks] = {};
+        uint64_t       my_len = 0, es = 1;
+        if (is_root) {
+            const auto &v = gv ? a_.dst.info_v : a_.src.info_v;
+            es            = ucc_dt_size(v.datatype);
+            for (uint32_t r = 0; r < n_; r++) {
+                cnt[r] = coll_count_at(a_, v.counts, r) * es;
+                dsp[r] = coll_disp_at(a_, v.displacements, r) * es;
+            }
+            if (!gv && !inplace) {
+                my_len = a_.dst.info.count *
+                         ucc_dt_size(a_.dst.info.datatype);
+            }
+            fa->c.src = gv ? (inplace ? nullptr : a_.src.info.buffer)
+                           : a_.src.info_v.buffer;
+            fa->c.dst = gv ? a_.dst.info_v.buffer
+                           : (inplace ? nullptr : a_.dst.info.buffer);
+        } else {
+            const auto &i = gv ? a_.src.info : a_.dst.info;
+            es            = ucc_dt_size(i.datatype);
+            my_len        = i.count * es;
+            fa->c.src     = gv ? a_.src.info.buffer : nullptr;
+            fa->c.dst     = gv ? nullptr : a_.dst.info.buffer;
+        }
+        if (!fused_plan_init_rooted_v(pl, gv ? FUSED_GATHERV : FUSED_SCATTERV,
+                                      (int)n_, (int)me_, (int)a_.root, cnt,
+                                      dsp, my_len, B, es, inplace)) {
+            *pl               = FusedPlan{};
+            pl->bound         = B;
+            pl->scratch_bytes = kFusedRootedHdr + B;
+            pl->fits_local    = false;
+        }
+        fa->root       = (int)a_.root;
+        fa->is_scatter = gv ? 0 : 1;
+        fa->fits_local = pl->fits_local ? 1 : 0;
+        fa->my_len     = pl->my_len;
+        fa->bound      = pl->bound;
+        for (uint32_t r = 0; r < n_; r++) {
+            fa->tab_off[r] = pl->tab_off[r];
+            fa->tab_len[r] = pl->tab_len[r];
+        }
+    }
+
+    /* built on first need, kept across re-posts of a persistent request */
+    ucc_status_t make_inner()
+    {
+        if (inner_) {
+            return UCC_OK;
+        }
+        return tt_->init_unfused(a_, tt_->team_, &inner_, &inner_alg_);
+    }
+
+    Task       *inner_     = nullptr;
+    const char *inner_alg_ = "";
+    size_t      bound_     = 0;
 };
 
 /* Staged linear collectives: allreduce / allgather(v) / reduce_scatter(v) /
@@ -4024,6 +4278,21 @@ class Cdna4Tl final : public Tl {
                     "persistent zero-copy reduce_scatter included; "
                     "one-shot requests gain up to 1m "
                     "(profiles/fused_colls.md)");
+        cfg.declare("TL_CDNA4", "FUSED_GATHER_SCATTER", "0",
+                    "serve small full-team device gather, scatter, gatherv "
+                    "and scatterv with one fused kernel per rank (algorithm "
+                    "'fused', score 100), independently of FUSED_COLLS and "
+                    "within FUSED_COLLS_MAX: gather takes the per-rank "
+                    "block, scatter n blocks, each rounded up to 16. "
+                    "gatherv and scatterv, whose counts only the root "
+                    "knows, take a 144-byte header off the bound, "
+                    "B = MAX - 144 rounded down to 16; the root decides "
+                    "inside the kernel: gatherv fits if the largest block "
+                    "is at most B, scatterv if the sum of the blocks, each "
+                    "rounded up to 16, is at most B; otherwise all ranks "
+                    "fall back together to staged_linear. gather and "
+                    "scatter are hipGraph-replayable; must be the same on "
+                    "every rank");
         if (!cfg.get_bool("TL_CDNA4", "ENABLE", true) ||
             !mc::hip_available()) {
             return nullptr;
@@ -4094,6 +4363,8 @@ class Cdna4Tl final : public Tl {
         c.fused_colls = cfg.get_bool("TL_CDNA4", "FUSED_COLLS", false);
         c.fused_colls_max =
             cfg.get_size("TL_CDNA4", "FUSED_COLLS_MAX", 8 * 1024);
+        c.fused_gather_scatter =
+            cfg.get_bool("TL_CDNA4", "FUSED_GATHER_SCATTER", false);
         return new Cdna4TlTeam(tlc, team, c);
     }
 };
@@ -4199,8 +4470,10 @@ ucc_status_t Cdna4TlTeam::init_unfused(const ucc_coll_args_t &args, Team *t,
                                        Task **task, const char **alg)
 {
     /* get_scores() below registers gated_pipeline for the v-forms exactly
-     * when GATED is set */
-    if (Config::instance().get_bool("TL_CDNA4", "GATED", true) &&
+     * when GATED is set, and never for gatherv and scatterv */
+    const bool rooted_v = args.coll_type == UCC_COLL_TYPE_GATHERV ||
+                          args.coll_type == UCC_COLL_TYPE_SCATTERV;
+    if (!rooted_v && Config::instance().get_bool("TL_CDNA4", "GATED", true) &&
         init_gated(args, t, task) == UCC_OK) {
         *alg = "gated_pipeline";
         return UCC_OK;
@@ -4271,10 +4544,10 @@ void Cdna4TlTeam::get_scores(Team *team, ScoreMap &map)
         };
         map.add(UCC_COLL_TYPE_BCAST, UCC_MEMORY_TYPE_CUDA, r);
     }
-    if (cfg_.fused_colls) {
-        /* opt-in (UCC_TL_CDNA4_FUSED_COLLS): unset, the map is exactly the
-         * entries below. A declined request (over the bound, in-place
-         * alltoall, ...) falls through to them. */
+    /* the score-100 entry of the fused one-kernel collectives, for the
+     * types a knob switches on: the task class follows the type, the
+     * declines are the same for all of them */
+    auto add_fused = [&](std::initializer_list<ucc_coll_type_t> types) {
         ScoreRange r;
         r.start    = 0;
         r.end      = SIZE_MAX;
@@ -4284,9 +4557,13 @@ void Cdna4TlTeam::get_scores(Team *team, ScoreMap &map)
         r.init     = [self](const ucc_coll_args_t &args, Team *t,
                         Task **task) -> ucc_status_t {
             const bool a2av = args.coll_type == UCC_COLL_TYPE_ALLTOALLV;
+            const bool rooted_v =
+                args.coll_type == UCC_COLL_TYPE_GATHERV ||
+                args.coll_type == UCC_COLL_TYPE_SCATTERV;
             if ((args.mask & UCC_COLL_ARGS_FIELD_ACTIVE_SET) ||
-                !(a2av ? FusedA2avTask::supported(args, self)
-                       : FusedCollTask::supported(args, self))) {
+                !(a2av       ? FusedA2avTask::supported(args, self)
+                  : rooted_v ? FusedRootedVTask::supported(args, self)
+                             : FusedCollTask::supported(args, self))) {
                 return UCC_ERR_NOT_SUPPORTED;
             }
             /* spinning kernels of several ranks of one process can share
@@ -4300,21 +4577,34 @@ void Cdna4TlTeam::get_scores(Team *team, ScoreMap &map)
             }
             if (a2av) {
                 *task = new FusedA2avTask(t->ctx, self, args);
+            } else if (rooted_v) {
+                *task = new FusedRootedVTask(t->ctx, self, args);
             } else {
                 *task = new FusedCollTask(t->ctx, self, args);
             }
             return UCC_OK;
         };
-        for (auto ct : {UCC_COLL_TYPE_ALLGATHER, UCC_COLL_TYPE_REDUCE_SCATTER,
-                        UCC_COLL_TYPE_ALLTOALL, UCC_COLL_TYPE_BCAST,
-                        UCC_COLL_TYPE_REDUCE, UCC_COLL_TYPE_ALLGATHERV,
-                        UCC_COLL_TYPE_REDUCE_SCATTERV,
-                        UCC_COLL_TYPE_ALLTOALLV}) {
+        for (auto ct : types) {
             for (auto mt :
                  {UCC_MEMORY_TYPE_CUDA, UCC_MEMORY_TYPE_CUDA_MANAGED}) {
                 map.add(ct, mt, r);
             }
         }
+    };
+    if (cfg_.fused_colls) {
+        /* opt-in (UCC_TL_CDNA4_FUSED_COLLS): unset, the map is exactly the
+         * entries below. A declined request (over the bound, in-place
+         * alltoall, ...) falls through to them. */
+        add_fused({UCC_COLL_TYPE_ALLGATHER, UCC_COLL_TYPE_REDUCE_SCATTER,
+                   UCC_COLL_TYPE_ALLTOALL, UCC_COLL_TYPE_BCAST,
+                   UCC_COLL_TYPE_REDUCE, UCC_COLL_TYPE_ALLGATHERV,
+                   UCC_COLL_TYPE_REDUCE_SCATTERV, UCC_COLL_TYPE_ALLTOALLV});
+    }
+    if (cfg_.fused_gather_scatter) {
+        /* opt-in of its own (UCC_TL_CDNA4_FUSED_GATHER_SCATTER), whatever
+         * FUSED_COLLS says: unset, the four types keep staged_linear */
+        add_fused({UCC_COLL_TYPE_GATHER, UCC_COLL_TYPE_SCATTER,
+                   UCC_COLL_TYPE_GATHERV, UCC_COLL_TYPE_SCATTERV});
     }
     add(UCC_COLL_TYPE_ALLREDUCE, 0, cfg_.fused_max, 100, "fused", true);
     if (Config::instance().get_bool("TL_CDNA4", "GATED", true)) {
